@@ -17,7 +17,16 @@ time includes that sum.  value = the frame's samples / max-over-ranks time.
 torch.distributed (gloo) only carries the communicator id, the barriers and
 the max of the rank times.
 
-Extra fields:
+A plain run sets up, warms up, times the steps and prints the result line.
+--dump-outputs DIR writes what the last timed step computed -- the RGBW film
+the caller's buffer receives (rank 0's summed film with several GPUs) -- as
+DIR/film.npy in float32 (a fixed, seeded sample of its values if it were
+larger than 64 MB).  The scene and the per-sample random streams are fixed,
+so two runs with the same arguments render the same inputs.
+
+Extra fields, measured after the timed region and only with --full (each can
+be left out of a --full run with --no-roofline / --no-parity /
+--no-cpu-baseline):
   roofline     -- the traversal kernel k_extend (north_star's target) against
                   the 8 TB/s HBM peak: algorithmic bytes per launch (48 B per
                   extension ray + the scene's primitive/node bytes, SURVEY.md
@@ -262,6 +271,24 @@ def hip_runtime():
     return libs
 
 
+DUMP_LIMIT = 64 << 20  # bytes --dump-outputs writes at most, over all arrays
+
+
+def dump_outputs(dirname, arrays, limit=DUMP_LIMIT):
+    """Write {name: array} as dirname/<name>.npy in float32 (float64 arrays stay
+    float64).  An array over its share of `limit` bytes is cut down to a fixed
+    sample of its flattened values (seeded: the same indices in every run)."""
+    os.makedirs(dirname, exist_ok=True)
+    budget = limit // max(len(arrays), 1)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+        if a.nbytes > budget:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, budget // a.itemsize, replace=False))
+            a = a.ravel()[idx]
+        np.save(os.path.join(dirname, f"{name}.npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -276,6 +303,11 @@ def main():
     ap.add_argument("--spp", type=int, default=0)
     ap.add_argument("--pool", type=int, default=0)
     ap.add_argument("--shard", default="passes", choices=["passes", "blocks"])
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's film as DIR/film.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the roofline, the parity with the CPU oracle "
+                         "and the CPU baseline (each can be left out again with its --no-* option)")
     ap.add_argument("--cpu-seconds", type=float, default=6.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-parity", action="store_true")
@@ -284,6 +316,9 @@ def main():
                     help="profiling helper: one warm-up and one measuring render with one pool part "
                          "(the render bench.py's roofline times), then exit")
     args = ap.parse_args()
+    do_roofline = args.full and not args.no_roofline
+    do_parity = args.full and not args.no_parity
+    do_cpu_baseline = args.full and not args.no_cpu_baseline
 
     # one process per GPU: a plain `bench.py --gpus N` starts the launcher
     # itself (a child process, before this process touches the GPU) and
@@ -355,7 +390,10 @@ def main():
     sync()
     elapsed = time.perf_counter() - t0
     last = r.last_stats
-    film_host = film.cpu().numpy() if rank == 0 and world == 1 else None  # the last timed step's image
+    # the last timed step's image (rank 0 holds the summed film of a sharded render)
+    film_host = film.cpu().numpy() if rank == 0 and (args.dump_outputs or (world == 1 and do_parity)) else None
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"film": film_host})
     rank_ms = [elapsed / args.steps * 1e3]
     comm_ranks = None
     if world > 1:
@@ -373,7 +411,7 @@ def main():
     value = samples_per_step * args.steps / elapsed / 1e6
 
     roof = None
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and do_roofline:
         os.environ["NORI_POOL_PARTS"] = "1"
         r.render(passes=share[1], pass_begin=share[0], blocks=share[2], path_pool=args.pool)
         r.render(passes=share[1], pass_begin=share[0], blocks=share[2], path_pool=args.pool, timing=True)
@@ -421,16 +459,16 @@ def main():
             "stream_parts": last.get("stream_parts", 1),
             "hip_runtime": hip_runtime(),
         }
-        if world == 1 and not args.no_parity and args.config == "c2":
+        if world == 1 and do_parity and args.config == "c2":
             out["parity"] = parity_full(scene, film_host, W, H, spp)
-        elif world == 1 and not args.no_parity:
+        elif world == 1 and do_parity:
             small = {"c2": (512, 512, 16), "c3": (128, 128, 4), "c4": (128, 128, 8), "c5": (160, 120, 8)}
             pw, ph, ps = small[args.config]
             pxml = xml if args.config != "c3" else configs.heightfield_scene(tmp, n=512, width=pw, height=ph, spp=ps)
             if args.config == "c4":
                 pxml = configs.envmap_scene(tmp, pw, ph, ps)
             out["parity"] = parity_check(pxml, pw, ph, ps)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and do_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(xml, W, H, args.cpu_seconds)
         else:
             out["cpu_baseline"] = None

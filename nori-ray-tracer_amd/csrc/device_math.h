@@ -10,7 +10,15 @@
 #endif
 #include <stdint.h>
 
+// hipRTC writes the embedded headers into a temporary directory under their
+// names: a name with ../ in it would land outside that directory, in a place
+// shared with (and possibly owned by) other users, so the ABI header is
+// embedded as plain "nori_gpu.h" (Makefile, rtc_headers.inc)
+#ifdef __HIPCC_RTC__
+#include "nori_gpu.h"
+#else
 #include "../../include/nori_gpu.h"
+#endif
 
 #define ND __device__ __forceinline__
 #define NHD __host__ __device__ __forceinline__

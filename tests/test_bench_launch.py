@@ -41,6 +41,26 @@ def test_rank_of_a_launched_job_runs_in_place():
     assert b.launch_plan(8, env, 8, []) is None
 
 
+def test_dump_outputs_writes_float32_within_the_limit(tmp_path):
+    """--dump-outputs: DIR/<name>.npy in float32 (float64 stays); an array over
+    its share of the byte limit becomes the same seeded sample in every run."""
+    import numpy as np
+
+    b = _bench()
+    assert b.DUMP_LIMIT == 64 << 20
+    film = np.arange(8 * 8 * 4, dtype=np.float32).reshape(8, 8, 4)
+    big = np.arange(1000, dtype=np.float64)
+    for d in ("a", "b"):
+        b.dump_outputs(str(tmp_path / d), {"film": film, "big": big, "ints": np.arange(5)}, limit=3 * 2048)
+    got = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in ("film", "big", "ints")}
+    assert got["film"].dtype == np.float32 and np.array_equal(got["film"], film)
+    assert got["ints"].dtype == np.float32 and np.array_equal(got["ints"], np.arange(5))
+    assert got["big"].dtype == np.float64 and got["big"].nbytes <= 2048
+    assert np.all(np.diff(got["big"]) > 0) and np.isin(got["big"], big).all()  # distinct values of the array
+    assert np.array_equal(got["big"], np.load(tmp_path / "b" / "big.npy"))
+    assert sum(a.nbytes for a in got.values()) <= 3 * 2048
+
+
 @pytest.mark.parametrize("gpus,env,devices", [
     (2, {"WORLD_SIZE": "4"}, 8),   # --gpus disagrees with the launcher
     (4, {"WORLD_SIZE": "4", "LOCAL_WORLD_SIZE": "4"}, 2),  # more local ranks than GPUs

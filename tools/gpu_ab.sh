@@ -9,6 +9,7 @@ L=$GRAFT_REPO_ROOT/nori-ray-tracer_amd/lib
 cfgs=""
 for c in $1; do case $c in @*) c="NORI_GPU_LIB=$L/libnori_gpu_${c#@}.so";; esac; cfgs="$cfgs $c"; done
 shift
+set -- --full "$@"  # the roofline fields printed below are measured only with --full
 reps=${REPS:-3}
 for r in $(seq 1 $reps); do
   for c in $cfgs; do

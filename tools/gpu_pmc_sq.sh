@@ -11,7 +11,7 @@ for g in "${groups[@]}"; do
   d=gpurun_out/pmcsq_${tag}_$i
   mkdir -p $d
   timeout -k 10 400 rocprofv3 --pmc $g --kernel-trace --output-format csv -d $d -o run -- \
-      python3 bench.py --no-cpu-baseline --no-parity "$@" > $d/bench.log 2>&1
+      python3 bench.py --full --no-cpu-baseline --no-parity "$@" > $d/bench.log 2>&1
   rc=$?; echo "group $i rc=$rc"; if [ $rc -ne 0 ]; then exit $rc; fi
   i=$((i+1))
 done

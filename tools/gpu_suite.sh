@@ -27,7 +27,7 @@ fi
 for c in $configs; do
   [ $c = none ] && continue
   extra=""; [ $c != c2 ] && extra="--steps 3 --warmup 1"
-  timeout -k 10 400 python bench.py --config $c $extra > $out/bench_$c.log 2>&1 || { echo "bench $c failed"; tail -5 $out/bench_$c.log; exit 1; }
+  timeout -k 10 400 python bench.py --full --config $c $extra > $out/bench_$c.log 2>&1 || { echo "bench $c failed"; tail -5 $out/bench_$c.log; exit 1; }
   grep '^{' $out/bench_$c.log | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('$c', round(d['value'],1), 'frac', round(d['roofline']['frac'],4), 'cpu', d['cpu_baseline'] and round(d['cpu_baseline']['value'],2), 'parity', d.get('parity',{}).get('l2'))"
 done
 if [ $s64 = 1 ]; then
