@@ -26,6 +26,9 @@
  *   nori_write_png        <- Bitmap::saveToLDR            src/bitmap.cpp:122-139
  *   nori_film_variance    <- renderScene's variance image src/render.cpp:164-169,190-245
  *   nori_denoise          <- denoiser/denoiser.py:53-66 (NL-means)
+ *   nori_film_block_error, nori_gpu_block_error, nori_gpu_render_adaptive
+ *                         (adaptive sampling: no reference counterpart, the
+ *                          reference gives every pixel sampleCount passes)
  *   nori_scene_bvh_info   <- BVH::build/statistics        src/bvh.cpp:329-402
  *   nori_scene_scan_list  (introspection: the small-scene scan list and its
  *                          exact in-plane filters, for the CPU tests)
@@ -256,6 +259,22 @@ int nori_write_png(const char *path, const float *rgb, int width, int height);
  * 263-276: the spread of the running mean over the passes) does not estimate
  * the pixel variance; this one does (deviation D5). */
 int nori_film_variance(const nori_scene_desc *scene, const float *stats, float *out);
+/* The adaptive sampler's error metric (no reference counterpart: the
+ * reference samples uniformly; deviation D11).  This is its one
+ * statement; the device kernel (nori_gpu_block_error) computes the same.
+ * Per pixel, from its 8 statistics floats (S1_c, S2_c for c = r, g, b, then n):
+ *   n < 2: e_p = 0, otherwise
+ *   m_c = S1_c / n,   v_c = max(0, S2_c - S1_c^2 / n) / (n (n - 1)),
+ *   e_p = sqrt(v_r + v_g + v_b) / sqrt(m_r + m_g + m_b + 1e-3)
+ * -- the standard error of the pixel mean relative to the square root of its
+ * brightness.  Per 32x32 block: the block is tiled from its own origin into
+ * 8x8 sub-tiles, each sub-tile's value is the mean of e_p over its pixels
+ * inside the frame (a sub-tile wholly outside the frame does not exist), and
+ * E_b is the MAXIMUM of the sub-tile means: one noisy corner (a caustic, a
+ * light's edge) is not averaged away by 900 quiet pixels.
+ * stats: H x W x 8 (render_desc.variance_out); errors: one float per frame
+ * block, id = by*nbx + bx.  Host function, double precision. */
+int nori_film_block_error(const nori_scene_desc *scene, const float *stats, float *errors);
 
 /* NL-means denoiser <- denoiser/denoiser.py:53-66 on the GPU.  rgb: H x W x 3
  * image, variance: H x W per-pixel variance (the script's grey variance
@@ -380,6 +399,50 @@ int nori_gpu_create(const nori_scene_desc *scene, int device, nori_gpu_ctx **out
  * owned, host or device memory).  Blocking. */
 int nori_gpu_render(nori_gpu_ctx *ctx, const nori_gpu_render_desc *desc,
                     float *rgbw_out, nori_gpu_stats *stats);
+/* nori_film_block_error on the context's device: stats is H x W x 8 floats in
+ * host memory, or (stats_on_device != 0) in device memory on the context's
+ * device, 16-byte aligned; errors is a HOST array of one float per frame
+ * block.  The difference S2 - S1^2/n is taken in fp64, the rest in fp32: the
+ * result agrees with the host function to fp32 rounding.  Blocking. */
+int nori_gpu_block_error(nori_gpu_ctx *ctx, const float *stats, int stats_on_device, float *errors);
+
+/* Adaptive sampling: blocks whose error metric E_b (nori_film_block_error)
+ * has fallen to `threshold` stop early; the others go on to the cap. */
+typedef struct nori_gpu_adaptive_desc {
+    uint32_t min_passes;     /* first round, >= 2 */
+    uint32_t max_passes;     /* per-block cap; 0 = scene sampleCount */
+    float    threshold;      /* a block stops once E_b <= threshold */
+    uint32_t reserved;       /* must be 0; pads passes_out to 8 bytes */
+    uint32_t *passes_out;    /* host, one per frame block: passes rendered (0 = block not selected); may be NULL */
+    float    *error_out;     /* host, one per frame block: E_b of the final statistics; may be NULL */
+} nori_gpu_adaptive_desc;
+/* Renders in rounds.  Round 0 renders passes [pass_begin, pass_begin +
+ * min_passes) of every selected block.  After each round E_b of the blocks
+ * just rendered is evaluated on the device; a block stays active while
+ * E_b > threshold and its pass count is below the cap, and the next round
+ * renders as many passes again as the active blocks have had, clamped to the
+ * cap (counts min, 2 min, 4 min, ..., max), continuing their pass numbering.
+ * So block b receives exactly the samples of passes [pass_begin, pass_begin +
+ * passes_out[b]): the film equals plain nori_gpu_render calls with those
+ * counts.  E_b is evaluated after the last round too.
+ * From `desc`: pass_begin, seed, num_blocks / block_ids, output_on_device,
+ * path_pool, timing and variance_out keep their nori_gpu_render meaning
+ * (film and statistics are ADDED into the caller's buffers, once, at the
+ * end); pass_count is ignored.  The metric is that of this call's samples:
+ * statistics are collected on the device whether or not variance_out is set.
+ * stats: samples, invalid_samples, the ray counters, iterations and the ms_*
+ * kernel times are summed over the rounds; ms_total is the wall time of the
+ * call.  nori_gpu_cancel is honoured between and within rounds
+ * (NORI_ERR_CANCELLED; nothing is added to host buffers then), and
+ * nori_gpu_progress rises over the whole call as samples done over the upper
+ * bound cap x selected pixels.  NORI_ERR_INVALID: min_passes < 2, a cap below
+ * min_passes, a negative or NaN threshold (+inf is valid: one round),
+ * reserved != 0.  Works for the wavefront and the one-bounce integrators.
+ * There is no sharded form: per-pixel statistics are not summed across ranks
+ * (nori_gpu_render_sharded); callers who drive rounds over several GPUs sum
+ * the statistics themselves and use nori_film_block_error. */
+int nori_gpu_render_adaptive(nori_gpu_ctx *ctx, const nori_gpu_render_desc *desc,
+                             const nori_gpu_adaptive_desc *ad, float *rgbw_out, nori_gpu_stats *stats);
 /* Trace n rays (host arrays; ray = o.xyz, mint, d.xyz, maxt) with the
  * reference's BVH semantics: closest hit, or any hit when any_hit != 0. */
 int nori_gpu_trace(nori_gpu_ctx *ctx, const float *rays, uint32_t n, int any_hit,

@@ -7,8 +7,11 @@
 //   (the reference calls stb_image_write; here zlib deflate, filter type 0).
 // nori_film_variance: variance of each pixel's mean radiance from the
 //   statistics nori_gpu_render accumulates (render_desc.variance_out).
+// nori_film_block_error: the adaptive sampler's per-block error from the same
+//   statistics (host version of block_error.hip).
 #include <zlib.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -84,5 +87,40 @@ extern "C" int nori_film_variance(const nori_scene_desc *scene, const float *sta
             out[3 * i + c] = (float)v;
         }
     }
+    return NORI_OK;
+}
+
+// The adaptive sampler's block error; the metric is stated at its declaration
+// (nori_gpu.h).  The device version is k_block_error (block_error.hip).
+extern "C" int nori_film_block_error(const nori_scene_desc *scene, const float *stats, float *errors) {
+    if (!scene || !stats || !errors) return NORI_ERR_INVALID;
+    const int W = scene->camera.width, H = scene->camera.height, bs = NORI_BLOCK_SIZE, sub = 8;
+    if (W <= 0 || H <= 0) return NORI_ERR_INVALID;
+    const int nbx = (W + bs - 1) / bs, nby = (H + bs - 1) / bs;
+    for (int by = 0; by < nby; ++by)
+        for (int bx = 0; bx < nbx; ++bx) {
+            double worst = 0.0;
+            for (int ty = by * bs; ty < std::min((by + 1) * bs, H); ty += sub)
+                for (int tx = bx * bs; tx < std::min((bx + 1) * bs, W); tx += sub) {
+                    double sum = 0.0;
+                    int count = 0;
+                    for (int y = ty; y < std::min(ty + sub, H); ++y)
+                        for (int x = tx; x < std::min(tx + sub, W); ++x) {
+                            const float *s = stats + 8 * ((size_t)y * W + x);
+                            const double n = s[6];
+                            ++count;
+                            if (n < 2.0) continue;
+                            double v = 0.0, m = 0.0;
+                            for (int c = 0; c < 3; ++c) {
+                                const double s1 = s[c], s2 = s[3 + c];
+                                v += std::max(0.0, s2 - s1 * s1 / n) / (n * (n - 1.0));
+                                m += s1 / n;
+                            }
+                            sum += std::sqrt(v) / std::sqrt(m + 1e-3);
+                        }
+                    worst = std::max(worst, sum / count);
+                }
+            errors[(size_t)by * nbx + bx] = (float)worst;
+        }
     return NORI_OK;
 }

@@ -125,5 +125,13 @@ hipError_t launch_denoise(const float *img, const float *var, int W, int H, int 
                           float *out, hipStream_t st);
 hipError_t launch_splat(const DevScene &S, const float4 *rec, const SplatDesc &sd, uint32_t nblocks, float *film,
                         Counters *C, hipStream_t st);
+// The adaptive sampler's block error (block_error.hip; the metric is stated
+// at nori_film_block_error in nori_gpu.h): stats W x H x 8 on the device
+// (16-byte aligned), ids = the nblocks frame blocks to evaluate (null: blocks
+// 0 .. nblocks-1), err = one float per frame block, written at the block's id.
+hipError_t launch_block_error(const float *stats, int W, int H, int nbx, const uint32_t *ids, uint32_t nblocks,
+                              float *err, hipStream_t st);
+// dst[i] += src[i], i < n (device buffers)
+hipError_t launch_add_into(float *dst, const float *src, size_t n, hipStream_t st);
 
 }  // namespace nori

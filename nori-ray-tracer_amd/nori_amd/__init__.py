@@ -26,7 +26,7 @@ from ._abi import NoriError, check, lib  # noqa: F401
 
 __all__ = ["load_scene", "Scene", "GpuRenderer", "RenderThread", "NoriError", "device_count",
            "develop", "write_exr", "write_png", "read_exr", "film_variance", "ldr_bytes", "variance_gray",
-           "denoise", "read_image"]
+           "denoise", "read_image", "block_error"]
 
 
 def _fptr(a):
@@ -144,6 +144,18 @@ def film_variance(scene, stats):
         raise ValueError(f"statistics shape {stats.shape} != {(scene.height, scene.width, 8)}")
     out = np.zeros((scene.height, scene.width, 3), np.float32)
     check(lib().nori_film_variance(scene.desc_ptr, _fptr(stats), _fptr(out)))
+    return out
+
+
+def block_error(scene, stats):
+    """The adaptive sampler's error E_b of every 32x32 block (one float per frame block, id = by*nbx + bx)
+    from (H, W, 8) sample statistics, on the host in double precision (nori_film_block_error, where
+    the metric is stated).  GpuRenderer.block_error is the device version."""
+    stats = np.ascontiguousarray(stats, dtype=np.float32)
+    if stats.shape != (scene.height, scene.width, 8):
+        raise ValueError(f"statistics shape {stats.shape} != {(scene.height, scene.width, 8)}")
+    out = np.zeros(scene.num_blocks(), np.float32)
+    check(lib().nori_film_block_error(scene.desc_ptr, _fptr(stats), _fptr(out)))
     return out
 
 
@@ -327,6 +339,57 @@ class GpuRenderer:
         rd.path_pool = int(path_pool)
         rd.timing = int(bool(timing))
         return rd, ids
+
+    def block_error(self, stats):
+        """block_error() of the scene on the GPU (nori_gpu_block_error): `stats` is an (H, W, 8)
+        float32 array, or an int device address of such a buffer (e.g. a torch tensor's data_ptr())."""
+        out = np.zeros(self.scene.num_blocks(), np.float32)
+        if isinstance(stats, np.ndarray):
+            stats = np.ascontiguousarray(stats, dtype=np.float32)
+            if stats.shape != (self.scene.height, self.scene.width, 8):
+                raise ValueError(f"statistics shape {stats.shape} != {(self.scene.height, self.scene.width, 8)}")
+            check(lib().nori_gpu_block_error(self._h, C.c_void_p(stats.ctypes.data), 0, _fptr(out)))
+        else:
+            check(lib().nori_gpu_block_error(self._h, C.c_void_p(int(stats)), 1, _fptr(out)))
+        return out
+
+    def render_adaptive(self, threshold, min_passes=8, max_passes=None, pass_begin=0, blocks=None, seed=0, out=None,
+                        device_ptr=None, variance=None, path_pool=0):
+        """Adaptive render (nori_gpu_render_adaptive): every block of `blocks` (all if None) gets
+        min_passes passes, then rounds that double its count until its error E_b (block_error) is at
+        most `threshold` or the count reaches max_passes (None: the scene's spp).
+
+        Returns (film, passes, errors): the RGBW film as render() returns it (None with `device_ptr`),
+        the passes each frame block received (0: not selected) and E_b of its final statistics.
+        `out`, `device_ptr` and `variance` are render()'s."""
+        rd, ids = self._desc(0, pass_begin, blocks, seed, path_pool, False)
+        ad = _abi.AdaptiveDesc()
+        ad.min_passes = int(min_passes)
+        ad.max_passes = int(self.scene.spp if max_passes is None else max_passes)
+        ad.threshold = float(threshold)
+        passes = np.zeros(self.scene.num_blocks(), np.uint32)
+        errors = np.zeros(self.scene.num_blocks(), np.float32)
+        ad.passes_out = passes.ctypes.data_as(C.POINTER(C.c_uint32))
+        ad.error_out = _fptr(errors)
+        if variance is not None:
+            if device_ptr is not None:
+                rd.variance_out = int(variance)
+            else:
+                assert (isinstance(variance, np.ndarray) and variance.dtype == np.float32 and variance.flags.c_contiguous
+                        and variance.shape == (self.scene.height, self.scene.width, 8))
+                rd.variance_out = variance.ctypes.data
+        st = _abi.Stats()
+        if device_ptr is not None:
+            rd.output_on_device = 1
+            film = C.c_void_p(int(device_ptr))
+        else:
+            if out is None:
+                out = np.zeros(self.scene.film_shape(), np.float32)
+            assert out.dtype == np.float32 and out.flags.c_contiguous and out.shape == self.scene.film_shape()
+            film = out.ctypes.data_as(C.c_void_p)
+        check(lib().nori_gpu_render_adaptive(self._h, C.byref(rd), C.byref(ad), film, C.byref(st)))
+        self.last_stats = st.as_dict()
+        return (None if device_ptr is not None else out), passes, errors
 
     def render_sharded(self, comm, device_ptr, passes=None, pass_begin=0, blocks=None, mode="passes", root=0,
                        seed=0, path_pool=0, timing=False, variance=None):

@@ -97,6 +97,12 @@ class RenderDesc(C.Structure):
                 ("variance_out", C.c_void_p)]
 
 
+class AdaptiveDesc(C.Structure):
+    _fields_ = [("min_passes", C.c_uint32), ("max_passes", C.c_uint32), ("threshold", C.c_float),
+                ("reserved", C.c_uint32), ("passes_out", C.POINTER(C.c_uint32)),
+                ("error_out", C.POINTER(C.c_float))]
+
+
 class Stats(C.Structure):
     _fields_ = [("samples", C.c_uint64), ("invalid_samples", C.c_uint64), ("rays_closest", C.c_uint64),
                 ("rays_shadow", C.c_uint64), ("rays_finish", C.c_uint64), ("iterations", C.c_uint64),
@@ -129,6 +135,7 @@ SIGNATURES = {
     "nori_write_exr": (C.c_int, [C.c_char_p, C.POINTER(C.c_float), C.c_int, C.c_int]),
     "nori_write_png": (C.c_int, [C.c_char_p, C.POINTER(C.c_float), C.c_int, C.c_int]),
     "nori_film_variance": (C.c_int, [C.POINTER(SceneDesc), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "nori_film_block_error": (C.c_int, [C.POINTER(SceneDesc), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "nori_denoise": (C.c_int, [C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.c_int, C.c_int,
                                C.c_int, C.c_float, C.c_int, C.POINTER(C.c_float)]),
     "nori_read_exr": (C.c_int, [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_float)]),
@@ -140,6 +147,9 @@ SIGNATURES = {
     "nori_gpu_device_count": (C.c_int, [C.POINTER(C.c_int)]),
     "nori_gpu_create": (C.c_int, [C.POINTER(SceneDesc), C.c_int, C.POINTER(C.c_void_p)]),
     "nori_gpu_render": (C.c_int, [C.c_void_p, C.POINTER(RenderDesc), C.c_void_p, C.POINTER(Stats)]),
+    "nori_gpu_block_error": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_float)]),
+    "nori_gpu_render_adaptive": (C.c_int, [C.c_void_p, C.POINTER(RenderDesc), C.POINTER(AdaptiveDesc), C.c_void_p,
+                                           C.POINTER(Stats)]),
     "nori_gpu_trace": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_uint32, C.c_int, C.POINTER(Hit)]),
     "nori_gpu_cancel": (C.c_int, [C.c_void_p]),
     "nori_gpu_progress": (C.c_float, [C.c_void_p]),
