@@ -29,6 +29,10 @@
  *   nori_film_block_error, nori_gpu_block_error, nori_gpu_render_adaptive
  *                         (adaptive sampling: no reference counterpart, the
  *                          reference gives every pixel sampleCount passes)
+ *   nori_gpu_render_features, nori_film_features, nori_film_denoise_guided,
+ *   nori_denoise_guided   (first-hit feature buffers and the feature-guided
+ *                          denoiser: no reference counterpart, the reference
+ *                          writes radiance and its variance image only)
  *   nori_scene_bvh_info   <- BVH::build/statistics        src/bvh.cpp:329-402
  *   nori_scene_scan_list  (introspection: the small-scene scan list and its
  *                          exact in-plane filters, for the CPU tests)
@@ -286,6 +290,49 @@ int nori_film_block_error(const nori_scene_desc *scene, const float *stats, floa
  * (convolve2d mode 'same').  Host buffers; runs on `device`. */
 int nori_denoise(int device, const float *rgb, const float *variance, int width, int height, int radius,
                  int patch, float k, int mode, float *out);
+/* First-hit features (nori_gpu_render_features): features (H x W x 8 sums) ->
+ * out (H x W x 7): mean albedo (3), mean shading normal (3), mean depth (1) =
+ * sum / count in double precision; a pixel with count 0 gives zeros; the
+ * normal is the mean, NOT renormalised.  Host function. */
+int nori_film_features(const nori_scene_desc *scene, const float *features, float *out);
+
+/* Feature-guided NL-means denoiser (no reference counterpart: the reference's
+ * script filters on colour alone; deviation D12).  This is its one
+ * statement; nori_film_denoise_guided computes it on the host in double
+ * precision, nori_denoise_guided on the GPU in fp32.
+ *   rgb      H x W x 3 linear radiance I
+ *   variance H x W     variance v of the pixel mean (the channels of
+ *                      nori_film_variance summed)
+ *   feat7    H x W x 7 nori_film_features: albedo a, normal n, depth z
+ * Pixels outside the frame do not exist (no wrap-around, no zero fill).  For a
+ * pixel p and every in-frame neighbour q = p + s, s in [-r, r]^2 (q = p included):
+ *   d2c(p,q) = the mean, over the patch offsets o in [-f, f]^2 for which both
+ *              p+o and q+o are inside the frame, of
+ *              ( sum_c (I_c(p+o) - I_c(q+o))^2 - (v(p+o) + min(v(p+o), v(q+o))) )
+ *              / ( eps + k^2 (v(p+o) + v(q+o)) )
+ *   d2f(p,q) = |a_p - a_q|^2 / sigma_albedo^2 + |n_p - n_q|^2 / sigma_normal^2
+ *              + ((z_p - z_q) / max(z_p, z_q, 1e-6))^2 / sigma_depth^2;
+ *              a term whose sigma is +inf is exactly 0
+ *   w(p,q)   = exp(-max(0, d2c)) exp(-d2f)
+ *   out(p)   = sum_q w(p,q) I(q) / sum_q w(p,q) */
+typedef struct nori_guided_desc {
+    int32_t radius;      /* r: neighbours q = p + s, s in [-r, r]^2, 0 <= r <= 8          */
+    int32_t patch;       /* f: patch offsets o in [-f, f]^2, 0 <= f <= 3                   */
+    float   k;           /* colour distance scale (> 0)                                    */
+    float   eps;         /* > 0                                                             */
+    float   sigma_albedo, sigma_normal, sigma_depth;   /* > 0; +inf switches a term off     */
+    uint32_t reserved;   /* must be 0 */
+} nori_guided_desc;
+/* NORI_ERR_INVALID (both): a null pointer, a non-positive size, radius or
+ * patch out of range, a non-positive or NaN k, eps or sigma, reserved != 0. */
+int nori_film_denoise_guided(const float *rgb, const float *variance, const float *feat7,
+                             int width, int height, const nori_guided_desc *d, float *out);   /* host, fp64 */
+/* Host buffers; runs on `device`.  Also NORI_ERR_INVALID (nothing launched)
+ * when the tile staging of (radius, patch) exceeds the device's LDS per
+ * work-group. */
+int nori_denoise_guided(int device, const float *rgb, const float *variance, const float *feat7,
+                        int width, int height, const nori_guided_desc *d, float *out);        /* GPU, host buffers */
+
 /* Read the R, G, B planes of a scanline OpenEXR file (NONE/ZIPS/ZIP, HALF or
  * FLOAT) <- Bitmap::Bitmap (bitmap.cpp:23-80).  Call with rgb = NULL to get
  * the size, then with a buffer of 3*width*height floats (row-major). */
@@ -443,6 +490,31 @@ typedef struct nori_gpu_adaptive_desc {
  * the statistics themselves and use nori_film_block_error. */
 int nori_gpu_render_adaptive(nori_gpu_ctx *ctx, const nori_gpu_render_desc *desc,
                              const nori_gpu_adaptive_desc *ad, float *rgbw_out, nori_gpu_stats *stats);
+/* First-hit features of the camera samples of passes [pass_begin, pass_begin+pass_count)
+ * of the selected blocks, ADDED into `features` (H x W x 8 floats, host or device memory
+ * as desc->output_on_device says; 16-byte aligned on the device):
+ *   0..2 albedo (sum)   3..5 world-space shading normal, signed (sum)
+ *   6    hit distance t along the primary ray (sum)   7 camera samples taken (count)
+ * Sample (pass k, pixel) draws from the renderer's own stream of that sample
+ * (jitter, then aperture sample), so its primary ray is the render's, for
+ * every camera; with chromatic aberration the features follow the green
+ * channel's ray.  Hit: the normal is the shading normal (normal-mapped where
+ * the mesh has a map: the vector the `normals` integrator returns before its
+ * fabs), the depth is t, the albedo is by BSDF: diffuse -- the albedo texture
+ * at the hit's uv; microfacet -- kd; disney -- base_color; mirror and
+ * dielectric -- (1, 1, 1).  Emission plays no part.  Miss: only the count
+ * rises, so a missed sample is recognisable by its zero normal.
+ * Each pixel's eight values are read, the samples added in pass order and the
+ * sums written back: no atomics, so the result is bitwise reproducible and a
+ * pass range split over several calls gives the identical buffer.  Works on a
+ * context of any integrator (no path pool).  From `desc`: pass_count 0 = the
+ * scene's sampleCount; path_pool is ignored; timing: the kernel time in
+ * stats->ms_shade; variance_out must be NULL (NORI_ERR_INVALID otherwise).
+ * stats: samples, rays_closest (one per sample), ms_total.  nori_gpu_cancel is
+ * honoured between chunks of passes (NORI_ERR_CANCELLED; a host buffer is left
+ * unchanged then) and nori_gpu_progress rises over the call.  Blocking. */
+int nori_gpu_render_features(nori_gpu_ctx *ctx, const nori_gpu_render_desc *desc,
+                             float *features, nori_gpu_stats *stats);
 /* Trace n rays (host arrays; ray = o.xyz, mint, d.xyz, maxt) with the
  * reference's BVH semantics: closest hit, or any hit when any_hit != 0. */
 int nori_gpu_trace(nori_gpu_ctx *ctx, const float *rays, uint32_t n, int any_hit,

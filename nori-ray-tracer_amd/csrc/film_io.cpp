@@ -9,6 +9,9 @@
 //   statistics nori_gpu_render accumulates (render_desc.variance_out).
 // nori_film_block_error: the adaptive sampler's per-block error from the same
 //   statistics (host version of block_error.hip).
+// nori_film_features: first-hit feature sums -> per-pixel means.
+// nori_film_denoise_guided: the feature-guided denoiser in double precision
+//   (host statement of k_guided, denoise.hip).
 #include <zlib.h>
 
 #include <algorithm>
@@ -121,6 +124,92 @@ extern "C" int nori_film_block_error(const nori_scene_desc *scene, const float *
                     worst = std::max(worst, sum / count);
                 }
             errors[(size_t)by * nbx + bx] = (float)worst;
+        }
+    return NORI_OK;
+}
+
+// First-hit feature sums (nori_gpu_render_features) -> per-pixel means.
+extern "C" int nori_film_features(const nori_scene_desc *scene, const float *features, float *out) {
+    if (!scene || !features || !out) return NORI_ERR_INVALID;
+    if (scene->camera.width <= 0 || scene->camera.height <= 0) return NORI_ERR_INVALID;
+    const size_t n_px = (size_t)scene->camera.width * (size_t)scene->camera.height;
+    for (size_t i = 0; i < n_px; ++i) {
+        const float *s = features + 8 * i;
+        const double n = s[7];
+        for (int c = 0; c < 7; ++c) out[7 * i + c] = n > 0.0 ? (float)((double)s[c] / n) : 0.0f;
+    }
+    return NORI_OK;
+}
+
+bool nori::guided_desc_valid(const nori_guided_desc *d) {
+    if (!d) return false;
+    if (d->radius < 0 || d->radius > 8 || d->patch < 0 || d->patch > 3 || d->reserved != 0) return false;
+    for (float v : {d->k, d->eps, d->sigma_albedo, d->sigma_normal, d->sigma_depth})
+        if (!(v > 0.0f)) return false;  // (NaN fails the comparison)
+    return true;
+}
+
+// The feature-guided denoiser, stated at its declaration (nori_gpu.h); the
+// device version is k_guided (denoise.hip).
+extern "C" int nori_film_denoise_guided(const float *rgb, const float *variance, const float *feat7, int width,
+                                        int height, const nori_guided_desc *d, float *out) {
+    if (!rgb || !variance || !feat7 || !out || width <= 0 || height <= 0 || !nori::guided_desc_valid(d))
+        return NORI_ERR_INVALID;
+    const int W = width, H = height, R = d->radius, F = d->patch;
+    const double k2 = (double)d->k * (double)d->k, eps = d->eps;
+    // 1 / sigma^2; 0 switches the term off (a sigma of +inf)
+    auto inv2 = [](float s) { return std::isinf(s) ? 0.0 : 1.0 / ((double)s * (double)s); };
+    const double ia = inv2(d->sigma_albedo), in = inv2(d->sigma_normal), iz = inv2(d->sigma_depth);
+    for (int py = 0; py < H; ++py)
+        for (int px = 0; px < W; ++px) {
+            const size_t p = (size_t)py * W + px;
+            const float *fp = feat7 + 7 * p;
+            double acc[3] = {0, 0, 0}, wsum = 0.0;
+            for (int sy = -R; sy <= R; ++sy)
+                for (int sx = -R; sx <= R; ++sx) {
+                    const int qy = py + sy, qx = px + sx;
+                    if (qy < 0 || qy >= H || qx < 0 || qx >= W) continue;
+                    const size_t q = (size_t)qy * W + qx;
+                    double sum = 0.0;
+                    int count = 0;
+                    for (int oy = -F; oy <= F; ++oy)
+                        for (int ox = -F; ox <= F; ++ox) {
+                            const int ay = py + oy, ax = px + ox, by = qy + oy, bx = qx + ox;
+                            if (ay < 0 || ay >= H || ax < 0 || ax >= W || by < 0 || by >= H || bx < 0 || bx >= W)
+                                continue;
+                            const size_t a = (size_t)ay * W + ax, b = (size_t)by * W + bx;
+                            double sq = 0.0;
+                            for (int c = 0; c < 3; ++c) {
+                                const double e = (double)rgb[3 * a + c] - (double)rgb[3 * b + c];
+                                sq += e * e;
+                            }
+                            const double va = variance[a], vb = variance[b];
+                            sum += (sq - (va + std::min(va, vb))) / (eps + k2 * (va + vb));
+                            ++count;
+                        }
+                    const double d2c = sum / count;  // (o = 0 always counts)
+                    const float *fq = feat7 + 7 * q;
+                    double d2f = 0.0;
+                    if (ia != 0.0) {
+                        double t = 0.0;
+                        for (int c = 0; c < 3; ++c) t += ((double)fp[c] - fq[c]) * ((double)fp[c] - fq[c]);
+                        d2f += t * ia;
+                    }
+                    if (in != 0.0) {
+                        double t = 0.0;
+                        for (int c = 3; c < 6; ++c) t += ((double)fp[c] - fq[c]) * ((double)fp[c] - fq[c]);
+                        d2f += t * in;
+                    }
+                    if (iz != 0.0) {
+                        const double zp = fp[6], zq = fq[6];
+                        const double rel = (zp - zq) / std::max(std::max(zp, zq), 1e-6);
+                        d2f += rel * rel * iz;
+                    }
+                    const double w = std::exp(-std::max(0.0, d2c)) * std::exp(-d2f);
+                    for (int c = 0; c < 3; ++c) acc[c] += w * (double)rgb[3 * q + c];
+                    wsum += w;
+                }
+            for (int c = 0; c < 3; ++c) out[3 * p + c] = (float)(acc[c] / wsum);
         }
     return NORI_OK;
 }

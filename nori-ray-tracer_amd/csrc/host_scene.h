@@ -94,4 +94,8 @@ void build_photon_map(const std::vector<float> &raw, uint32_t n, float radius, s
                       std::vector<uint32_t> &rgbe, std::vector<float> &tables, std::vector<uint32_t> &start,
                       uint32_t &mask);
 
+// The guided denoiser's parameter rules (film_io.cpp; nori_guided_desc in
+// nori_gpu.h): the host statement and the device entry point share them.
+bool guided_desc_valid(const nori_guided_desc *d);
+
 }  // namespace nori

@@ -123,6 +123,18 @@ hipError_t launch_direct(const DevScene &S, const WorkDesc &wd, float4 *rec, Cou
 size_t denoise_lds_bytes(int R, int P);
 hipError_t launch_denoise(const float *img, const float *var, int W, int H, int R, int P, float k, int mode,
                           float *out, hipStream_t st);
+// Feature-guided denoiser (denoise.hip k_guided; stated at
+// nori_film_denoise_guided in nori_gpu.h): img W x H x 3, var W x H, feat
+// W x H x 7, radius R, patch half-width F; a sigma of +inf switches its term off.
+size_t guided_lds_bytes(int R, int F);
+hipError_t launch_guided(const float *img, const float *var, const float *feat, int W, int H, int R, int F, float k,
+                         float eps, float sigma_a, float sigma_n, float sigma_z, float *out, hipStream_t st);
+// First-hit features (kernels_features.hip k_features): one thread per entry
+// of `pixels` (M entries, y*W + x) adds the samples of passes [pass_begin,
+// pass_begin + np) in pass order to the pixel's eight sums in feat (W x H x 8,
+// 16-byte aligned): albedo, shading normal, hit distance, sample count.
+hipError_t launch_features(const DevScene &S, const uint32_t *pixels, uint32_t M, uint32_t pass_begin, uint32_t np,
+                           uint64_t seed, float *feat, int stack, hipStream_t st);
 hipError_t launch_splat(const DevScene &S, const float4 *rec, const SplatDesc &sd, uint32_t nblocks, float *film,
                         Counters *C, hipStream_t st);
 // The adaptive sampler's block error (block_error.hip; the metric is stated

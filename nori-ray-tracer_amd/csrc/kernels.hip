@@ -23,10 +23,11 @@
 
 #include <cstdlib>
 
-// The kernels are compiled in three translation units so that hipcc builds
-// them in parallel: NORI_TU 0 (this file) = everything but the two largest
-// groups, 1 (kernels_shade.hip) = k_shade + launch_shade, 2
-// (kernels_finish.hip) = k_finish + launch_finish.  Templates are shared;
+// The kernels are compiled in four translation units so that hipcc builds
+// them in parallel: NORI_TU 0 (this file) = everything but the groups named
+// next, 1 (kernels_shade.hip) = k_shade + launch_shade, 2
+// (kernels_finish.hip) = k_finish + launch_finish, 3 (kernels_features.hip)
+// = k_features + launch_features.  Templates are shared;
 // each non-template kernel and launcher lives in exactly one unit.
 #ifndef NORI_TU
 #define NORI_TU 0
@@ -1810,14 +1811,18 @@ struct OneBounce {
     const DevScene &S;
     uint32_t *stk;
     uint32_t rc = 0, rs = 0;  // rays traced: closest, shadow
-    ND bool closest(V3 o, V3 d, float mint, float maxt, SurfHit &hs) {
+    ND bool closest(V3 o, V3 d, float mint, float maxt, SurfHit &hs, float &t) {  // t: the hit distance
         ++rc;
         TRay r{o, d, V3{0, 0, 0}, mint, maxt};
-        float t, u, v;
+        float u, v;
         uint32_t p;
         if (!traverse<STACK, false>(S, r, stk, t, p, u, v)) return false;
         hs = surface(S, p, t, u, v, o, d);
         return true;
+    }
+    ND bool closest(V3 o, V3 d, float mint, float maxt, SurfHit &hs) {
+        float t;
+        return closest(o, d, mint, maxt, hs, t);
     }
     ND bool occluded(V3 o, V3 d, float maxt) {
         ++rs;
@@ -2037,6 +2042,69 @@ __global__ __launch_bounds__(kTraceBlock) void k_direct(DevScene S, WorkDesc wd,
         atomicAdd(&C->direct_rays[1], (unsigned long long)rs);
     }
 }
+
+// ------------------------------------------------------------------ first-hit features
+// nori_gpu_render_features (no reference counterpart): the albedo, shading
+// normal and hit distance at the first hit of every camera sample, summed per
+// pixel for the guided denoiser.  One thread per selected pixel loops over the
+// passes: sample (pass, pixel) draws its jitter and aperture sample from the
+// stream k_direct / k_shade give that sample, so its ray is the render's
+// primary ray; with chromatic aberration the green channel's ray.  The
+// thread reads the pixel's eight sums, adds the samples in pass order and
+// writes them back with two 16-byte stores: no atomics, so the buffer is
+// bitwise reproducible and independent of how a pass range is split.
+#if NORI_TU == 3
+template <int STACK>
+__global__ __launch_bounds__(kTraceBlock) void k_features(DevScene S, const uint32_t *pixels, uint32_t M,
+                                                          uint32_t pass_begin, uint32_t np, uint64_t seed,
+                                                          float4 *feat) {
+    __shared__ uint32_t stk[stack_words(STACK) * kTraceBlock];
+    const uint32_t e = blockIdx.x * kTraceBlock + threadIdx.x;
+    if (e >= M) return;
+    OneBounce<STACK> ob{S, stk + threadIdx.x};
+    const uint32_t pix = pixels[e];
+    const uint32_t y = pix / (uint32_t)S.W, x = pix - y * (uint32_t)S.W;
+    float4 f0 = feat[2 * (size_t)pix], f1 = feat[2 * (size_t)pix + 1];
+    const int ch = (S.chromatic[0] != 0.0f || S.chromatic[1] != 0.0f || S.chromatic[2] != 0.0f) ? 1 : -1;
+    for (uint32_t k = 0; k < np; ++k) {
+        Pcg rng;
+        wave_seed(rng, seed, (uint64_t)(pass_begin + k) * ((uint64_t)S.W * (uint64_t)S.H) + pix);
+        const V2 jit = next2D(rng);
+        const V2 ap = next2D(rng);  // apertureSample (render.cpp:99)
+        V3 o, d;
+        float mn, mx, t;
+        camera_sample(S, (float)x + jit.x, (float)y + jit.y, ap, ch, o, d, mn, mx);
+        SurfHit hs;
+        if (ob.closest(o, d, mn, mx, hs, t)) {
+            const DevBsdf &B = S.bsdfs[S.shapes[hs.shape].bsdf];
+            V3 a{1, 1, 1};  // mirror, dielectric
+            if (B.type == NORI_BSDF_DIFFUSE) a = albedo_at(B, hs.uv);
+            else if (B.type == NORI_BSDF_MICROFACET) a = V3{B.kd[0], B.kd[1], B.kd[2]};
+            else if (B.type == NORI_BSDF_DISNEY) a = V3{B.base[0], B.base[1], B.base[2]};
+            f0.x += a.x, f0.y += a.y, f0.z += a.z;
+            f0.w += hs.sh.n.x, f1.x += hs.sh.n.y, f1.y += hs.sh.n.z;
+            f1.z += t;
+        }
+        f1.w += 1.0f;
+    }
+    feat[2 * (size_t)pix] = f0;
+    feat[2 * (size_t)pix + 1] = f1;
+}
+
+hipError_t launch_features(const DevScene &S, const uint32_t *pixels, uint32_t M, uint32_t pass_begin, uint32_t np,
+                           uint64_t seed, float *feat, int stack, hipStream_t st) {
+    if (M == 0 || np == 0) return hipSuccess;
+    const dim3 g((M + kTraceBlock - 1) / kTraceBlock), b(kTraceBlock);
+    float4 *f = reinterpret_cast<float4 *>(feat);
+    switch (stack) {
+    case 0: hipLaunchKernelGGL(k_features<0>, g, b, 0, st, S, pixels, M, pass_begin, np, seed, f); break;
+    case 8: hipLaunchKernelGGL(k_features<8>, g, b, 0, st, S, pixels, M, pass_begin, np, seed, f); break;
+    case 16: hipLaunchKernelGGL(k_features<16>, g, b, 0, st, S, pixels, M, pass_begin, np, seed, f); break;
+    default: hipLaunchKernelGGL(k_features<32>, g, b, 0, st, S, pixels, M, pass_begin, np, seed, f); break;
+    }
+    return hipGetLastError();
+}
+#endif
 
 // ------------------------------------------------------------------ photon tracing
 // PhotonMapper::preprocess (photonmapper.cpp:41-117), one thread per emitted

@@ -1637,6 +1637,82 @@ int render(nori_gpu_ctx &c, const nori_gpu_render_desc &rd, float *rgbw_out, nor
     return NORI_OK;
 }
 
+// nori_gpu_render_features: k_features over the selected blocks' pixels, in
+// chunks of passes (about 16M samples per launch) between which a cancel
+// request is honoured.  The kernel continues each pixel's sums from the values
+// in the buffer, so a host buffer is uploaded first and copied back after the
+// last chunk: host and device buffers receive the same bits.
+int render_features(nori_gpu_ctx &c, const nori_gpu_render_desc &rd, float *features, nori_gpu_stats *stats) {
+    const auto t0 = std::chrono::steady_clock::now();
+    HIP_TRY(hipSetDevice(c.device));
+    if (rd.variance_out) throw NoriException(NORI_ERR_INVALID, "nori_gpu_render_features: variance_out must be NULL");
+    work_lists(c, rd);
+    const uint32_t M = (uint32_t)c.hpixels.size(), passes = rd.pass_count ? rd.pass_count : c.spp;
+    if (passes == 0 || M == 0) throw NoriException(NORI_ERR_INVALID, "nothing to render (pass_count or blocks empty)");
+    const size_t n = 8 * (size_t)c.S.W * (size_t)c.S.H;
+    float *dev = features;
+    if (rd.output_on_device) {
+        if ((uintptr_t)features % 16) throw NoriException(NORI_ERR_INVALID, "device features must be 16-byte aligned");
+    } else {
+        c.varbuf.ensure(n * sizeof(float));
+        dev = c.varbuf.as<float>();
+        HIP_TRY(hipMemcpyAsync(dev, features, n * sizeof(float), hipMemcpyHostToDevice, c.stream));
+    }
+    c.cancel = 0;
+    c.report(0.0);
+    const uint32_t chunk = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(passes, ((uint64_t)1 << 24) / M));
+    Timers tm;
+    std::vector<std::array<hipEvent_t, 2>> spans;
+    uint64_t done = 0;
+    bool cancelled = false;
+    for (uint32_t p0 = 0; p0 < passes; p0 += chunk) {
+        if (c.cancel.load()) {
+            cancelled = true;
+            break;
+        }
+        const uint32_t np = std::min(chunk, passes - p0);
+        std::array<hipEvent_t, 2> ev{};
+        if (rd.timing) {
+            for (auto &e : ev) e = tm.get();
+            HIP_TRY(hipEventRecord(ev[0], c.stream));
+        }
+        HIP_TRY(launch_features(c.S, c.pixels.as<uint32_t>(), M, rd.pass_begin + p0, np, rd.seed, dev, c.stack,
+                                c.stream));
+        if (rd.timing) {
+            HIP_TRY(hipEventRecord(ev[1], c.stream));
+            spans.push_back(ev);
+        }
+        HIP_TRY(hipStreamSynchronize(c.stream));
+        done += (uint64_t)np * M;
+        c.report((double)(p0 + np) / passes);
+    }
+    double kms = 0.0;
+    for (const auto &e : spans) {
+        float a = 0;
+        HIP_TRY(hipEventElapsedTime(&a, e[0], e[1]));
+        kms += a;
+    }
+    if (!rd.output_on_device && !cancelled)
+        HIP_TRY(hipMemcpy(features, dev, n * sizeof(float), hipMemcpyDeviceToHost));
+    c.report(1.0);
+    if (stats) {
+        std::memset(stats, 0, sizeof(*stats));
+        stats->samples = done;
+        stats->rays_closest = done;  // one primary ray per sample
+        stats->scene_bytes = c.scene_bytes;
+        stats->bvh_nodes = c.bvh_nodes;
+        stats->bvh_depth = c.bvh_depth;
+        stats->stream_parts = 1;
+        stats->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        stats->ms_shade = kms;  // k_features
+        stats->scan_rtc = c.rtc.extend ? 1u : 0u;  // (k_features scans generically, like k_direct)
+        stats->scan_rtc_cached = c.rtc.cached ? 1u : 0u;
+        stats->ms_scan_rtc = c.rtc.compile_ms;
+    }
+    if (cancelled) return fail(NORI_ERR_CANCELLED, "rendering was cancelled");
+    return NORI_OK;
+}
+
 int frame_blocks(const nori_gpu_ctx &c, int *nbx_out = nullptr) {
     const int nbx = (c.S.W + NORI_BLOCK_SIZE - 1) / NORI_BLOCK_SIZE, nby = (c.S.H + NORI_BLOCK_SIZE - 1) / NORI_BLOCK_SIZE;
     if (nbx_out) *nbx_out = nbx;
@@ -1935,6 +2011,41 @@ int nori_denoise(int device, const float *rgb, const float *variance, int width,
         return (int)NORI_OK;
     });
 }
+// The feature-guided denoiser (nori_film_denoise_guided states it) on device
+// `device`: host buffers in, host buffer out.
+int nori_denoise_guided(int device, const float *rgb, const float *variance, const float *feat7, int width, int height,
+                        const nori_guided_desc *d, float *out) {
+    return guarded([&] {
+        if (!rgb || !variance || !feat7 || !out || width <= 0 || height <= 0 || !guided_desc_valid(d))
+            return fail(NORI_ERR_INVALID, "nori_denoise_guided: invalid arguments");
+        HIP_TRY(hipSetDevice(device));
+        {  // the tile + halo staging must fit one work-group's LDS
+            int lds_max = 0;
+            HIP_TRY(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, device));
+            const size_t need = guided_lds_bytes(d->radius, d->patch);
+            if (need > (size_t)lds_max)
+                return fail(NORI_ERR_INVALID, "nori_denoise_guided: radius " + std::to_string(d->radius) + " / patch " +
+                                                  std::to_string(d->patch) + " need " + std::to_string(need) +
+                                                  " bytes of LDS per work-group, the device has " +
+                                                  std::to_string(lds_max));
+        }
+        const size_t n = (size_t)width * (size_t)height;
+        DevBuf di, dv, df, dout;
+        di.ensure(12 * n);
+        dv.ensure(4 * n);
+        df.ensure(28 * n);
+        dout.ensure(12 * n);
+        HIP_TRY(hipMemcpy(di.p, rgb, 12 * n, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(dv.p, variance, 4 * n, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(df.p, feat7, 28 * n, hipMemcpyHostToDevice));
+        HIP_TRY(launch_guided((const float *)di.p, (const float *)dv.p, (const float *)df.p, width, height, d->radius,
+                              d->patch, d->k, d->eps, d->sigma_albedo, d->sigma_normal, d->sigma_depth,
+                              (float *)dout.p, nullptr));
+        HIP_TRY(hipDeviceSynchronize());
+        HIP_TRY(hipMemcpy(out, dout.p, 12 * n, hipMemcpyDeviceToHost));
+        return (int)NORI_OK;
+    });
+}
 int nori_gpu_abi_version(void) { return NORI_GPU_ABI_VERSION; }
 
 int nori_read_image(const char *path, int *width, int *height, uint8_t *rgb) {
@@ -2093,6 +2204,14 @@ int nori_gpu_render(nori_gpu_ctx *c, const nori_gpu_render_desc *rd, float *rgbw
         if (!c || !rd || !rgbw_out) return fail(NORI_ERR_INVALID, "null argument");
         if (rd->num_blocks && !rd->block_ids) return fail(NORI_ERR_INVALID, "block_ids is null");
         return render(*c, *rd, rgbw_out, stats);
+    });
+}
+
+int nori_gpu_render_features(nori_gpu_ctx *c, const nori_gpu_render_desc *rd, float *features, nori_gpu_stats *stats) {
+    return guarded([&] {
+        if (!c || !rd || !features) return fail(NORI_ERR_INVALID, "null argument");
+        if (rd->num_blocks && !rd->block_ids) return fail(NORI_ERR_INVALID, "block_ids is null");
+        return render_features(*c, *rd, features, stats);
     });
 }
 

@@ -26,7 +26,7 @@ from ._abi import NoriError, check, lib  # noqa: F401
 
 __all__ = ["load_scene", "Scene", "GpuRenderer", "RenderThread", "NoriError", "device_count",
            "develop", "write_exr", "write_png", "read_exr", "film_variance", "ldr_bytes", "variance_gray",
-           "denoise", "read_image", "block_error"]
+           "denoise", "read_image", "block_error", "film_features", "denoise_guided", "film_denoise_guided"]
 
 
 def _fptr(a):
@@ -204,6 +204,55 @@ def denoise(img, var, radius=3, patch=3, k=0.02, mode=0, device=0, script_scale=
     check(lib().nori_denoise(device, _fptr(src), _fptr(var), img.shape[1], img.shape[0], radius, patch, k, mode,
                              _fptr(out)))
     return out * np.float32(255) if script_scale else out
+
+
+def film_features(scene, feats):
+    """Per-pixel feature means (H, W, 7) -- albedo, shading normal (not renormalised), depth --
+    from the (H, W, 8) sums of GpuRenderer.features (nori_film_features); zeros where no sample fell."""
+    feats = np.ascontiguousarray(feats, dtype=np.float32)
+    if feats.shape != (scene.height, scene.width, 8):
+        raise ValueError(f"feature shape {feats.shape} != {(scene.height, scene.width, 8)}")
+    out = np.zeros((scene.height, scene.width, 7), np.float32)
+    check(lib().nori_film_features(scene.desc_ptr, _fptr(feats), _fptr(out)))
+    return out
+
+
+def _guided_args(img, var, feat7, radius, patch, k, eps, sigma_albedo, sigma_normal, sigma_depth):
+    img = np.ascontiguousarray(img, dtype=np.float32)
+    var = np.ascontiguousarray(var, dtype=np.float32)
+    feat7 = np.ascontiguousarray(feat7, dtype=np.float32)
+    if img.ndim != 3 or img.shape[2] != 3 or var.shape != img.shape[:2] or feat7.shape != img.shape[:2] + (7,):
+        raise ValueError(f"image {img.shape} / variance {var.shape} / features {feat7.shape}: "
+                         "expected (H, W, 3), (H, W) and (H, W, 7)")
+    d = _abi.GuidedDesc(int(radius), int(patch), float(k), float(eps), float(sigma_albedo), float(sigma_normal),
+                        float(sigma_depth), 0)
+    return img, var, feat7, d
+
+
+def denoise_guided(img, var, feat7, radius=5, patch=1, k=0.45, eps=1e-10, sigma_albedo=0.1, sigma_normal=0.25,
+                   sigma_depth=0.1, device=0):
+    """Feature-guided NL-means denoiser on the GPU (nori_denoise_guided; the filter is stated at
+    nori_film_denoise_guided in nori_gpu.h).
+
+    img: (H, W, 3) linear radiance; var: (H, W) variance of the pixel mean (film_variance(...)
+    summed over its channels); feat7: (H, W, 7) film_features().  The parameter values are
+    defaults, not tuned values; a sigma of inf switches its feature term off."""
+    img, var, feat7, d = _guided_args(img, var, feat7, radius, patch, k, eps, sigma_albedo, sigma_normal, sigma_depth)
+    out = np.empty_like(img)
+    check(lib().nori_denoise_guided(int(device), _fptr(img), _fptr(var), _fptr(feat7), img.shape[1], img.shape[0],
+                                    C.byref(d), _fptr(out)))
+    return out
+
+
+def film_denoise_guided(img, var, feat7, radius=5, patch=1, k=0.45, eps=1e-10, sigma_albedo=0.1, sigma_normal=0.25,
+                        sigma_depth=0.1):
+    """denoise_guided() on the host in double precision (nori_film_denoise_guided): the
+    filter's statement, which the GPU kernel is tested against."""
+    img, var, feat7, d = _guided_args(img, var, feat7, radius, patch, k, eps, sigma_albedo, sigma_normal, sigma_depth)
+    out = np.empty_like(img)
+    check(lib().nori_film_denoise_guided(_fptr(img), _fptr(var), _fptr(feat7), img.shape[1], img.shape[0],
+                                         C.byref(d), _fptr(out)))
+    return out
 
 
 class BvhInfo(C.Structure):
@@ -406,6 +455,29 @@ class GpuRenderer:
         check(lib().nori_gpu_render_sharded(self._h, comm.handle, C.byref(rd), _abi.SHARD_MODES[mode], int(root),
                                             C.c_void_p(int(device_ptr)), C.byref(st)))
         self.last_stats = st.as_dict()
+
+    def features(self, passes=None, pass_begin=0, blocks=None, seed=0, out=None, timing=False):
+        """First-hit features of the camera samples of passes [pass_begin, pass_begin+passes) of
+        `blocks` (all if None), on the render's own primary rays (nori_gpu_render_features).
+
+        Returns the (H, W, 8) float32 sums -- albedo (3), signed shading normal (3), hit distance,
+        sample count -- added into `out` when given.  `out` may also be an int device address of
+        such a buffer (16-byte aligned, e.g. a torch tensor's data_ptr()): the sums are then
+        added on the GPU and None is returned.  film_features() turns the sums into means."""
+        rd, ids = self._desc(passes, pass_begin, blocks, seed, 0, timing)
+        shape = (self.scene.height, self.scene.width, 8)
+        st = _abi.Stats()
+        if out is not None and not isinstance(out, np.ndarray):
+            rd.output_on_device = 1
+            check(lib().nori_gpu_render_features(self._h, C.byref(rd), C.c_void_p(int(out)), C.byref(st)))
+            self.last_stats = st.as_dict()
+            return None
+        if out is None:
+            out = np.zeros(shape, np.float32)
+        assert out.dtype == np.float32 and out.flags.c_contiguous and out.shape == shape
+        check(lib().nori_gpu_render_features(self._h, C.byref(rd), out.ctypes.data_as(C.c_void_p), C.byref(st)))
+        self.last_stats = st.as_dict()
+        return out
 
     def trace(self, rays, any_hit=False):
         """Scene::rayIntersect on a batch: rays (n, 8) = o.xyz, mint, d.xyz, maxt."""

@@ -103,6 +103,12 @@ class AdaptiveDesc(C.Structure):
                 ("error_out", C.POINTER(C.c_float))]
 
 
+class GuidedDesc(C.Structure):
+    _fields_ = [("radius", C.c_int32), ("patch", C.c_int32), ("k", C.c_float), ("eps", C.c_float),
+                ("sigma_albedo", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float),
+                ("reserved", C.c_uint32)]
+
+
 class Stats(C.Structure):
     _fields_ = [("samples", C.c_uint64), ("invalid_samples", C.c_uint64), ("rays_closest", C.c_uint64),
                 ("rays_shadow", C.c_uint64), ("rays_finish", C.c_uint64), ("iterations", C.c_uint64),
@@ -150,6 +156,12 @@ SIGNATURES = {
     "nori_gpu_block_error": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_float)]),
     "nori_gpu_render_adaptive": (C.c_int, [C.c_void_p, C.POINTER(RenderDesc), C.POINTER(AdaptiveDesc), C.c_void_p,
                                            C.POINTER(Stats)]),
+    "nori_gpu_render_features": (C.c_int, [C.c_void_p, C.POINTER(RenderDesc), C.c_void_p, C.POINTER(Stats)]),
+    "nori_film_features": (C.c_int, [C.POINTER(SceneDesc), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "nori_film_denoise_guided": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int,
+                                           C.c_int, C.POINTER(GuidedDesc), C.POINTER(C.c_float)]),
+    "nori_denoise_guided": (C.c_int, [C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                      C.c_int, C.c_int, C.POINTER(GuidedDesc), C.POINTER(C.c_float)]),
     "nori_gpu_trace": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_uint32, C.c_int, C.POINTER(Hit)]),
     "nori_gpu_cancel": (C.c_int, [C.c_void_p]),
     "nori_gpu_progress": (C.c_float, [C.c_void_p]),
