@@ -17,6 +17,12 @@
  *                            src/block.cpp:93-133)
  *   nori_gpu_trace        <- Scene::rayIntersect(ray, its) / rayIntersect(ray)
  *                            include/nori/scene.h:93-115 -> BVH::rayIntersect src/bvh.cpp:404-462
+ *   nori_gpu_query        <- Scene::rayIntersect(ray, its) with the whole Intersection
+ *                            include/nori/scene.h:93-115 + setHitInformation
+ *                            src/mesh.cpp:122-170, src/sphere.cpp:78-93
+ *                            (nori_scene_surface: the same record on the host)
+ *   nori_gpu_camera_rays  <- Camera::sampleRay src/perspective.cpp:90-112,
+ *                            src/thinlens.cpp:120-147, src/advancedCamera.cpp:85-157
  *   nori_gpu_cancel       <- RenderThread::stopRendering  src/render.cpp:63-71
  *   nori_gpu_progress     <- RenderThread::getProgress    src/render.cpp:73-78
  *   nori_film_develop     <- ImageBlock::toBitmap         src/block.cpp:76-82
@@ -519,6 +525,81 @@ int nori_gpu_render_features(nori_gpu_ctx *ctx, const nori_gpu_render_desc *desc
  * reference's BVH semantics: closest hit, or any hit when any_hit != 0. */
 int nori_gpu_trace(nori_gpu_ctx *ctx, const float *rays, uint32_t n, int any_hit,
                    nori_gpu_hit *hits);
+
+/* ---- ray queries with full hit records ------------------------------------
+ * Scene::rayIntersect(ray, its) + setHitInformation: one 64-byte record = four float4. */
+typedef struct nori_gpu_surface {
+    float p[3];   float t;        /* its.p ; its.t, +inf on a miss                         */
+    float ng[3];  int32_t prim;   /* its.geoFrame.n ; global primitive id, -1 on a miss    */
+    float ns[3];  int32_t shape;  /* its.shFrame.n (normal-mapped) ; shape index, -1 miss  */
+    float uv[2];  float bary[2];  /* its.uv after setHitInformation ; nori_gpu_hit's u, v   */
+} nori_gpu_surface;
+
+typedef struct nori_gpu_query_desc {
+    uint32_t n;          /* rays */
+    int32_t  any_hit;    /* as nori_gpu_trace; only with hits, surf must be NULL */
+    int32_t  on_device;  /* rays / hits / surf are device pointers on the context's device, 16-byte aligned */
+    uint32_t reserved;   /* must be 0 */
+} nori_gpu_query_desc;
+
+/* The record of hit i of ray i (8 floats: o.xyz, mint, d.xyz, maxt), on the
+ * host in fp32 with the kernels' operation order (no device needed).  This is
+ * the record's one statement; the device kernel (nori_gpu_query) computes the same.
+ *   bary, t, prim: the nori_gpu_hit values verbatim; shape: the shape that
+ *   owns primitive `prim` (primitives are numbered in shape order, a mesh
+ *   takes tri_count ids, a sphere one).
+ *   Mesh (vertices p0, p1, p2 of triangle prim, b = 1 - (u + v)):
+ *     p  = (b p0 + u p1) + v p2
+ *     ng = normalize(cross(p1 - p0, p2 - p0))
+ *     uv = (b uv0 + u uv1) + v uv2; the barycentrics (u, v) if the mesh has no uvs
+ *     ns = normalize((b n0 + u n1) + v n2); with a normal map (meshes with
+ *          normals only) the texel at uv (x = (int)(uv.x W), y = (int)(uv.y H),
+ *          wrapped or clamped as the image says), m = normalize(2 byte / 255 - 1)
+ *          per channel, taken from the frame of the interpolated normal
+ *          (Frame(n), common.cpp:274-283) to the world: ns = s m.x + t m.y + n m.z,
+ *          NOT renormalised (NormalMap::eval, mesh.cpp:147-155);
+ *          ns = ng if the mesh has no normals
+ *   Sphere (centre c): p = o + t d, ng = ns = normalize(p - c),
+ *     uv = (0.5 + acos(n.z) / (2 pi), phi / pi), phi = atan2(n.y, n.x) wrapped
+ *     to [0, 2 pi) (sphericalCoordinates, common.cpp:264-272) -- always
+ *     computed, whatever the BSDF
+ *   Miss (prim < 0): t = +inf, prim = shape = -1, every other float 0.
+ * NORI_ERR_INVALID: a null pointer, a primitive id outside the scene. */
+int nori_scene_surface(const nori_scene_desc *scene, uint32_t n, const float *rays,
+                       const nori_gpu_hit *hits, nori_gpu_surface *out);
+
+/* Trace desc->n rays as nori_gpu_trace does (the same kernels: `hits` is
+ * bit-identical to its result) and, with `surf`, fill the record of every
+ * closest hit (nori_scene_surface).  hits and surf may each be NULL, not both.
+ * on_device: the three pointers are device memory on the context's device,
+ * nothing is copied and nothing allocated per call (a context-owned hit
+ * buffer serves hits == NULL); the caller has made the rays ready before the
+ * call, as with nori_gpu_render's device film.  Otherwise they are host
+ * arrays, staged through context-owned device buffers that later calls reuse,
+ * in chunks of at most NORI_QUERY_CHUNK rays (environment, default 4194304).
+ * Blocking; runs on the context's stream: concurrent use with a render (or
+ * another query) on the same context is not supported.
+ * NORI_ERR_INVALID, nothing launched: a null ctx, desc or rays; both outputs
+ * null; any_hit with surf; reserved != 0; on_device with a pointer that is
+ * not 16-byte aligned.  n == 0 is a no-op.
+ * stats (may be NULL): rays_closest or rays_shadow (any_hit) = n, ms_total
+ * (wall time), ms_extend / ms_shade = HIP-event time of the trace / record kernels. */
+int nori_gpu_query(nori_gpu_ctx *ctx, const nori_gpu_query_desc *desc, const float *rays,
+                   nori_gpu_hit *hits, nori_gpu_surface *surf, nori_gpu_stats *stats);
+
+/* Camera::sampleRay for the renderer's own samples: the primary ray of sample
+ * (pass pass_begin + k, pixel pix = y W + x) at rays[8 (k H W + pix)] (o.xyz,
+ * mint, d.xyz, maxt), for k < pass_count and the pixels of the selected blocks
+ * (other entries are left untouched).  The sample draws from
+ * wave_seed(seed, (pass_begin + k) W H + pix): the jitter first, then the
+ * aperture sample -- what the integrators and nori_gpu_render_features do;
+ * with chromatic aberration it is the green channel's ray.  From `desc`:
+ * pass_begin, pass_count (0 = the scene's sampleCount), seed, num_blocks /
+ * block_ids and output_on_device (rays is device memory, 16-byte aligned);
+ * the other fields are ignored, variance_out must be NULL (NORI_ERR_INVALID).
+ * rays: pass_count x H x W x 8 floats.  Works on a context of any integrator.
+ * Blocking, on the context's stream. */
+int nori_gpu_camera_rays(nori_gpu_ctx *ctx, const nori_gpu_render_desc *desc, float *rays);
 int nori_gpu_cancel(nori_gpu_ctx *ctx);
 float nori_gpu_progress(const nori_gpu_ctx *ctx);
 void nori_gpu_destroy(nori_gpu_ctx *ctx);

@@ -135,6 +135,16 @@ hipError_t launch_guided(const float *img, const float *var, const float *feat, 
 // 16-byte aligned): albedo, shading normal, hit distance, sample count.
 hipError_t launch_features(const DevScene &S, const uint32_t *pixels, uint32_t M, uint32_t pass_begin, uint32_t np,
                            uint64_t seed, float *feat, int stack, hipStream_t st);
+// Hit records (kernels_query.hip k_surface; stated at nori_scene_surface in
+// nori_gpu.h): record i (four float4) of hit i (t, prim, u, v) of ray i (two
+// float4), i < n; all three arrays 16-byte aligned.
+hipError_t launch_surface(const DevScene &S, const float4 *rays, const float4 *hits, uint32_t n, float4 *out,
+                          hipStream_t st);
+// Primary rays (kernels_query.hip k_camera_rays): the ray of sample (pass
+// pass_begin + k, pixel pix) for k in [k0, k0 + np) and the M entries of
+// `pixels` (y*W + x), written at rays[8 * (k * W * H + pix)]; np * M < 2^31.
+hipError_t launch_camera_rays(const DevScene &S, const uint32_t *pixels, uint32_t M, uint32_t pass_begin, uint32_t k0,
+                              uint32_t np, uint64_t seed, float *rays, hipStream_t st);
 hipError_t launch_splat(const DevScene &S, const float4 *rec, const SplatDesc &sd, uint32_t nblocks, float *film,
                         Counters *C, hipStream_t st);
 // The adaptive sampler's block error (block_error.hip; the metric is stated

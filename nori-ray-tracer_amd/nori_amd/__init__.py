@@ -26,7 +26,8 @@ from ._abi import NoriError, check, lib  # noqa: F401
 
 __all__ = ["load_scene", "Scene", "GpuRenderer", "RenderThread", "NoriError", "device_count",
            "develop", "write_exr", "write_png", "read_exr", "film_variance", "ldr_bytes", "variance_gray",
-           "denoise", "read_image", "block_error", "film_features", "denoise_guided", "film_denoise_guided"]
+           "denoise", "read_image", "block_error", "film_features", "denoise_guided", "film_denoise_guided",
+           "scene_surface"]
 
 
 def _fptr(a):
@@ -78,6 +79,20 @@ class Scene:
     def positions(self):
         n = self.desc.num_vertices
         return np.ctypeslib.as_array(self.desc.positions, shape=(n, 3)).copy()
+
+    def normals(self):
+        """Per-vertex normals (num_vertices, 3); zeros for the vertices of meshes without normals."""
+        n = self.desc.num_vertices
+        if not self.desc.normals:
+            return np.zeros((n, 3), np.float32)
+        return np.ctypeslib.as_array(self.desc.normals, shape=(n, 3)).copy()
+
+    def uvs(self):
+        """Per-vertex texture coordinates (num_vertices, 2); zeros where a mesh has none."""
+        n = self.desc.num_vertices
+        if not self.desc.uvs:
+            return np.zeros((n, 2), np.float32)
+        return np.ctypeslib.as_array(self.desc.uvs, shape=(n, 2)).copy()
 
     def indices(self):
         n = self.desc.num_triangles
@@ -214,6 +229,25 @@ def film_features(scene, feats):
         raise ValueError(f"feature shape {feats.shape} != {(scene.height, scene.width, 8)}")
     out = np.zeros((scene.height, scene.width, 7), np.float32)
     check(lib().nori_film_features(scene.desc_ptr, _fptr(feats), _fptr(out)))
+    return out
+
+
+HIT_DTYPE = np.dtype([("t", "<f4"), ("prim", "<i4"), ("u", "<f4"), ("v", "<f4")])
+SURFACE_DTYPE = np.dtype([("p", "<f4", 3), ("t", "<f4"), ("ng", "<f4", 3), ("prim", "<i4"), ("ns", "<f4", 3),
+                          ("shape", "<i4"), ("uv", "<f4", 2), ("bary", "<f4", 2)])
+
+
+def scene_surface(scene, rays, hits):
+    """The hit records of `hits` (structured t, prim, u, v, as trace() returns them) of `rays`
+    (n, 8) on the host in fp32 (nori_scene_surface, where the record is stated; no GPU needed):
+    a structured array p, t, ng, prim, ns, shape, uv, bary.  GpuRenderer.query is the device version."""
+    rays = np.ascontiguousarray(rays, dtype=np.float32)
+    hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE)
+    if rays.ndim != 2 or rays.shape[1] != 8 or hits.shape != (rays.shape[0],):
+        raise ValueError(f"rays {rays.shape} / hits {hits.shape}: expected (n, 8) and (n,)")
+    out = np.zeros(rays.shape[0], SURFACE_DTYPE)
+    check(lib().nori_scene_surface(scene.desc_ptr, rays.shape[0], _fptr(rays), C.c_void_p(hits.ctypes.data),
+                                   C.c_void_p(out.ctypes.data)))
     return out
 
 
@@ -487,6 +521,59 @@ class GpuRenderer:
         check(lib().nori_gpu_trace(self._h, _fptr(rays), n, int(bool(any_hit)), hits))
         a = np.frombuffer(hits, dtype=np.dtype([("t", "<f4"), ("prim", "<i4"), ("u", "<f4"), ("v", "<f4")]))
         return a.copy()
+
+    def query(self, rays, any_hit=False, surface=True, hits_out=None, surf_out=None, n=None):
+        """Scene::rayIntersect(ray, its) on a batch, with the whole hit record (nori_gpu_query).
+
+        Host form: `rays` is an (n, 8) float32 array (o.xyz, mint, d.xyz, maxt); returns a dict
+        with "hits" (structured array t, prim, u, v -- the result of trace()) and, for a closest-hit
+        query with `surface`, "surf" (structured array p, t, ng, prim, ns, shape, uv, bary; the
+        record is stated at nori_scene_surface in nori_gpu.h).
+        Device form: `rays` is an int device address of n x 8 floats (`n` is required), `hits_out`
+        and `surf_out` are int device addresses of n x 16 and n x 64 bytes (either may be None, not
+        both; all 16-byte aligned, e.g. torch tensors' data_ptr()); nothing is copied and None is
+        returned.  The buffers must be ready before the call (torch.cuda.synchronize())."""
+        qd = _abi.QueryDesc(0, int(bool(any_hit)), 0, 0)
+        st = _abi.Stats()
+        if not isinstance(rays, np.ndarray):
+            if n is None:
+                raise ValueError("query: a device address needs n=")
+            qd.n, qd.on_device = int(n), 1
+            check(lib().nori_gpu_query(self._h, C.byref(qd), C.c_void_p(int(rays)),
+                                       None if hits_out is None else C.c_void_p(int(hits_out)),
+                                       None if surf_out is None else C.c_void_p(int(surf_out)), C.byref(st)))
+            self.last_stats = st.as_dict()
+            return None
+        rays = np.ascontiguousarray(rays, dtype=np.float32)
+        if rays.ndim != 2 or rays.shape[1] != 8:
+            raise ValueError(f"rays {rays.shape}: expected (n, 8)")
+        qd.n = rays.shape[0]
+        hits = np.zeros(qd.n, HIT_DTYPE)
+        surf = np.zeros(qd.n, SURFACE_DTYPE) if surface and not any_hit else None
+        check(lib().nori_gpu_query(self._h, C.byref(qd), C.c_void_p(rays.ctypes.data), C.c_void_p(hits.ctypes.data),
+                                   None if surf is None else C.c_void_p(surf.ctypes.data), C.byref(st)))
+        self.last_stats = st.as_dict()
+        return {"hits": hits} if surf is None else {"hits": hits, "surf": surf}
+
+    def camera_rays(self, passes=None, pass_begin=0, blocks=None, seed=0, out=None):
+        """Camera::sampleRay of the renderer's own samples (nori_gpu_camera_rays): the primary rays
+        of passes [pass_begin, pass_begin+passes) of `blocks` (all if None) as (passes, H, W, 8)
+        float32 (o.xyz, mint, d.xyz, maxt) -- the rays render() and features() trace for the same
+        seed.  Only the selected blocks' pixels are written (into `out` when given).  `out` may be
+        an int device address of such a buffer (16-byte aligned): None is returned then."""
+        rd, ids = self._desc(passes, pass_begin, blocks, seed, 0, False)
+        if rd.pass_count == 0:  # the library's "0 = the scene's sampleCount": the buffer is sized here
+            rd.pass_count = max(1, int(self.scene.spp))
+        shape = (rd.pass_count, self.scene.height, self.scene.width, 8)
+        if out is not None and not isinstance(out, np.ndarray):
+            rd.output_on_device = 1
+            check(lib().nori_gpu_camera_rays(self._h, C.byref(rd), C.c_void_p(int(out))))
+            return None
+        if out is None:
+            out = np.zeros(shape, np.float32)
+        assert out.dtype == np.float32 and out.flags.c_contiguous and out.shape == shape
+        check(lib().nori_gpu_camera_rays(self._h, C.byref(rd), C.c_void_p(out.ctypes.data)))
+        return out
 
     def cancel(self):
         check(lib().nori_gpu_cancel(self._h))

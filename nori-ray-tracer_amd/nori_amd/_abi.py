@@ -128,6 +128,16 @@ class Hit(C.Structure):
     _fields_ = [("t", C.c_float), ("prim", C.c_int32), ("u", C.c_float), ("v", C.c_float)]
 
 
+class Surface(C.Structure):
+    """nori_gpu_surface: the 64-byte hit record of nori_gpu_query / nori_scene_surface."""
+    _fields_ = [("p", C.c_float * 3), ("t", C.c_float), ("ng", C.c_float * 3), ("prim", C.c_int32),
+                ("ns", C.c_float * 3), ("shape", C.c_int32), ("uv", C.c_float * 2), ("bary", C.c_float * 2)]
+
+
+class QueryDesc(C.Structure):
+    _fields_ = [("n", C.c_uint32), ("any_hit", C.c_int32), ("on_device", C.c_int32), ("reserved", C.c_uint32)]
+
+
 # exported entry points: name -> (restype, argtypes)
 SIGNATURES = {
     "nori_gpu_last_error": (C.c_char_p, []),
@@ -163,6 +173,10 @@ SIGNATURES = {
     "nori_denoise_guided": (C.c_int, [C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float),
                                       C.c_int, C.c_int, C.POINTER(GuidedDesc), C.POINTER(C.c_float)]),
     "nori_gpu_trace": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_uint32, C.c_int, C.POINTER(Hit)]),
+    "nori_gpu_query": (C.c_int, [C.c_void_p, C.POINTER(QueryDesc), C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.POINTER(Stats)]),
+    "nori_scene_surface": (C.c_int, [C.POINTER(SceneDesc), C.c_uint32, C.POINTER(C.c_float), C.c_void_p, C.c_void_p]),
+    "nori_gpu_camera_rays": (C.c_int, [C.c_void_p, C.POINTER(RenderDesc), C.c_void_p]),
     "nori_gpu_cancel": (C.c_int, [C.c_void_p]),
     "nori_gpu_progress": (C.c_float, [C.c_void_p]),
     "nori_gpu_destroy": (None, [C.c_void_p]),
@@ -178,6 +192,9 @@ SIGNATURES = {
     "nori_gpu_comm_status_word": (C.c_int, [C.c_int, C.c_int]),
     "nori_gpu_comm_timeout": (C.c_double, [C.c_int, C.c_double, C.c_double, C.c_double]),
 }
+
+# entry points added without an ABI bump (no existing signature or struct changed)
+ADDED_IN_7 = {"nori_gpu_query", "nori_scene_surface", "nori_gpu_camera_rays"}
 
 COMM_ID_BYTES = 128
 SHARD_PASSES, SHARD_BLOCKS = 0, 1
@@ -224,6 +241,8 @@ def lib():
         _one_hip_runtime()
         l = C.CDLL(LIB_PATH)
         for name, (res, args) in SIGNATURES.items():
+            if name in ADDED_IN_7 and not hasattr(l, name):
+                continue  # an earlier build of ABI 7 (NORI_GPU_LIB): it still loads; using the call raises AttributeError
             fn = getattr(l, name)
             fn.restype = res
             fn.argtypes = args
