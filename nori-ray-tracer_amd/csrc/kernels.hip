@@ -1170,10 +1170,29 @@ constexpr uint32_t kSlotEmit = 1u << 31, kSlotEm = 1u << 30;  // above kWorkMask
 // known to point into LDS the compiler emits ds_read for the table reads; a
 // run-time select between the LDS and the global tables leaves generic
 // pointers, i.e. flat loads (vector-memory latency, both wait counters).
+// k_shade's arguments as one struct, its only parameter.  As ten parameters
+// the compiler read nearly all of them from the kernel-argument segment at the
+// kernel's top (C2's kernel: 34 of 36 scalar loads before the first barrier)
+// and held them to their uses: 106 SGPRs, the limit, in 10 of the 18
+// instantiations, and up to 76 SGPRs spilled to VGPR lanes (C2's kernel: 41
+// spilled, 41 v_writelane and 68 v_readlane instructions).  As fields of
+// one struct they are read where they are used: 65-102 SGPRs, none spilled,
+// in every instantiation.
+struct ShadeArgs {
+    DevScene S;
+    PathQueue in, out;
+    ShadowQueue sq;
+    SegState seg;
+    int in_sel;
+    WorkDesc wd;
+    float4 *rec;
+    Counters *C;
+    uint32_t lds_bytes;
+};
 template <int INTEG, bool LDS, int VAR>
 __global__ __launch_bounds__(kShadeBlock) __attribute__((amdgpu_waves_per_eu(NORI_SHADE_WAVES)))
-void k_shade(DevScene Sg, PathQueue in, PathQueue out, ShadowQueue sq, SegState seg, int in_sel, WorkDesc wd,
-             float4 *rec, Counters *C, uint32_t lds_bytes) {
+void k_shade(ShadeArgs args) {
+    const auto &[Sg, in, out, sq, seg, in_sel, wd, rec, C, lds_bytes] = args;
     static_assert(kShadeBlock == kSeg, "one shade thread per segment slot");
     // VAR: 0 basic plugins only (FULL = false), 1 full, 2 full + chromatic
     // aberration (the per-channel continuation is compiled in only then)
@@ -2602,10 +2621,9 @@ static void shade_dispatch(const DevScene &S, const PathQueue &in, const PathQue
     dim3 g(nseg), b(kShadeBlock);  // nseg segments from wd.b0 (wd.G counts the whole pool)
     // the shadow-ray slots overlay the blob, dead once the vertices are shaded
     const uint32_t dyn = S.nee_inline ? std::max(lds, kNeeSlotBytes) : lds;
-    if (lds)
-        hipLaunchKernelGGL((k_shade<INTEG, true, VAR>), g, b, dyn, st, S, in, out, sq, seg, in_sel, wd, rec, C, lds);
-    else
-        hipLaunchKernelGGL((k_shade<INTEG, false, VAR>), g, b, dyn, st, S, in, out, sq, seg, in_sel, wd, rec, C, 0u);
+    const ShadeArgs a{S, in, out, sq, seg, in_sel, wd, rec, C, lds};
+    if (lds) hipLaunchKernelGGL((k_shade<INTEG, true, VAR>), g, b, dyn, st, a);
+    else hipLaunchKernelGGL((k_shade<INTEG, false, VAR>), g, b, dyn, st, a);
 }
 template <int INTEG>
 static void shade_dispatch(const DevScene &S, const PathQueue &in, const PathQueue &out, const ShadowQueue &sq,
