@@ -855,9 +855,19 @@ static void set_hit_info(const oracle_scene *s, int si, uint32_t local, const Ra
     }
 }
 
-/* bvh.cpp:404-462 */
+/* bvh.cpp:404-462.  The reference walks with a fixed stack[64] and no check;
+ * here a walk that would push a 65th entry stops as a miss and counts itself
+ * in g_stack_overflows, and oracle_scene_create (photon pass), oracle_render
+ * and oracle_trace fail when the count moved during the call (calls running
+ * at the same time on other threads share the count: one of them overflowing
+ * fails them all, never the other way round).  ORACLE_BVH_STACK is lowered
+ * only by the test of this guard. */
+#ifndef ORACLE_BVH_STACK
+#define ORACLE_BVH_STACK 64
+#endif
+static atomic_uint g_stack_overflows;
 static int scene_intersect(const oracle_scene *s, const Ray *_ray, Its *its, int shadow) {
-    uint32_t node_idx = 0, stack_idx = 0, stack[64];
+    uint32_t node_idx = 0, stack_idx = 0, stack[ORACLE_BVH_STACK];
     its->t = F_INF;
     Ray ray = *_ray;
     if (ray.mint == EPS) {
@@ -874,6 +884,7 @@ static int scene_intersect(const oracle_scene *s, const Ray *_ray, Its *its, int
             continue;
         }
         if ((node->flag_size & 1u) == 0) {
+            if (stack_idx == ORACLE_BVH_STACK) { atomic_fetch_add(&g_stack_overflows, 1u); its->t = F_INF; return 0; }
             stack[stack_idx++] = node->start_right;
             node_idx++;
         } else {
@@ -1852,9 +1863,11 @@ int oracle_scene_create(const nori_scene_desc *d, oracle_scene **out) {
             if (s->emitters[i].type != NORI_EMITTER_AREA) { oracle_scene_free(s); return NORI_ERR_UNSUPPORTED; }
         s->ph_r = d->photon_radius;
         s->ph_norm = (s->ph_r * s->ph_r) * (float)d->photon_count;   /* photonmapper.cpp:177 */
+        const unsigned overflows = atomic_load(&g_stack_overflows);
         if (!(s->ph_r > 0) || d->photon_count == 0 || photon_preprocess(s) != 0) {
             oracle_scene_free(s); return NORI_ERR_INVALID;
         }
+        if (atomic_load(&g_stack_overflows) != overflows) { oracle_scene_free(s); return NORI_ERR_UNSUPPORTED; }
     }
     *out = s;
     return NORI_OK;
@@ -1988,6 +2001,7 @@ int oracle_render(const oracle_scene *s, int rng_mode, uint64_t seed, uint32_t p
                   const uint32_t *block_ids, uint32_t num_blocks, int nthreads, int variance_pass,
                   float *rgbw, oracle_stats *stats) {
     if (!s || !rgbw) return NORI_ERR_INVALID;
+    const unsigned overflows = atomic_load(&g_stack_overflows);
     if (pass_count == 0) pass_count = s->desc.sample_count;
     int nbx = (int)ceilf(s->W / (float)NORI_BLOCK_SIZE), nby = (int)ceilf(s->H / (float)NORI_BLOCK_SIZE);
     uint32_t total = (uint32_t)(nbx * nby);
@@ -2058,11 +2072,13 @@ int oracle_render(const oracle_scene *s, int rng_mode, uint64_t seed, uint32_t p
     pthread_barrier_destroy(&j.barrier);
     pthread_mutex_destroy(&j.merge_lock);
     free(th); free(order); free(j.block_rng); free(j.var_img); free(j.sum); free(j.sum2);
+    if (atomic_load(&g_stack_overflows) != overflows) return NORI_ERR_UNSUPPORTED;  /* scene_intersect's guard */
     return NORI_OK;
 }
 
 int oracle_trace(const oracle_scene *s, const float *rays, uint32_t n, int any_hit, nori_gpu_hit *hits) {
     if (!s || !rays || !hits) return NORI_ERR_INVALID;
+    const unsigned overflows = atomic_load(&g_stack_overflows);
     for (uint32_t i = 0; i < n; ++i) {
         const float *r = rays + 8 * (size_t)i;
         Ray ray = ray_make(v3(r[0], r[1], r[2]), v3(r[4], r[5], r[6]), r[3], r[7]);
@@ -2074,6 +2090,7 @@ int oracle_trace(const oracle_scene *s, const float *rays, uint32_t n, int any_h
         hits[i].v = hit && !any_hit ? its.v : 0.0f;
         if (hit && !any_hit && s->shapes[its.shape].type == NORI_SHAPE_SPHERE) { hits[i].u = 0; hits[i].v = 0; }
     }
+    if (atomic_load(&g_stack_overflows) != overflows) return NORI_ERR_UNSUPPORTED;  /* scene_intersect's guard */
     return NORI_OK;
 }
 

@@ -43,7 +43,10 @@ int oracle_scene_bvh_stats(const oracle_scene *s, uint32_t *nodes, float *sah, u
 
 /* render.cpp:173-250 pass loop.  Adds into rgbw ((H+2b)x(W+2b)x4).
  * rng_mode: NORI_RNG_WAVE or NORI_RNG_BLOCK.  nthreads<=0: all hw threads.
- * variance_pass: also run the reference's serial per-pass variance sweep. */
+ * variance_pass: also run the reference's serial per-pass variance sweep.
+ * oracle_render and oracle_trace return NORI_ERR_UNSUPPORTED (the output is
+ * then meaningless) when a BVH walk needed more than the reference's 64
+ * stack entries. */
 int oracle_render(const oracle_scene *s, int rng_mode, uint64_t seed,
                   uint32_t pass_begin, uint32_t pass_count,
                   const uint32_t *block_ids, uint32_t num_blocks,

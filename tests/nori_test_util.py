@@ -170,6 +170,73 @@ def compare_to_png(img, ref_lin, block=50, scale=1.0):
             "rel_max": float(rel.max())}
 
 
+def prim_hit(scene, rays, prim):
+    """Ray i against the one primitive prim[i] (global ids, as trace() reports them) in numpy
+    fp32: (hit, t, u, v).  The operation order is tri_hit / sphere_hit of scan.h with dot() and
+    cross() of device_math.h -- Mesh::rayIntersect (mesh.cpp:83-120) and Sphere::rayIntersect
+    (sphere.cpp:43-76), every +, -, *, / and sqrt rounded once to fp32, nothing fused -- and the
+    walk's adaptive epsilon (mint == 1e-4f grows with the origin's largest coordinate).  An
+    independent third statement of the test: the tie rule of test_gpu_parity._compare_hits and
+    the oracle's own t, u, v are checked against it (test_bvh_shapes.py)."""
+    f32 = np.float32
+    rays = np.ascontiguousarray(rays, f32)
+    prim = np.asarray(prim, np.int64)
+    n = rays.shape[0]
+    o, d = rays[:, 0:3], rays[:, 4:7]
+    mint, maxt = rays[:, 3].copy(), rays[:, 7]
+    eps = mint == f32(1e-4)
+    mint[eps] = np.maximum(mint[eps], mint[eps] * np.abs(o[eps]).max(axis=1))
+
+    def dot(a, b):
+        return (a[:, 0] * b[:, 0] + a[:, 1] * b[:, 1]) + a[:, 2] * b[:, 2]
+
+    def cross(a, b):
+        return np.stack([a[:, 1] * b[:, 2] - a[:, 2] * b[:, 1], a[:, 2] * b[:, 0] - a[:, 0] * b[:, 2],
+                         a[:, 0] * b[:, 1] - a[:, 1] * b[:, 0]], 1)
+
+    shapes = scene.shapes()
+    counts = [1 if sh.type == nori_amd._abi.SHAPE_SPHERE else sh.tri_count for sh in shapes]
+    first = np.concatenate([[0], np.cumsum(counts)])
+    shape = np.searchsorted(first, prim, side="right") - 1
+    sphere = np.array([sh.type == nori_amd._abi.SHAPE_SPHERE for sh in shapes])[shape]
+    hit, t = np.zeros(n, bool), np.full(n, np.inf, f32)
+    u, v = np.zeros(n, f32), np.zeros(n, f32)
+    with np.errstate(all="ignore"):
+        m = np.flatnonzero(~sphere)
+        if m.size:
+            tri = np.array([sh.tri_offset for sh in shapes], np.int64)[shape[m]] + (prim[m] - first[shape[m]])
+            p = scene.positions()[scene.indices()[tri]]
+            p0, e1, e2 = p[:, 0], p[:, 1] - p[:, 0], p[:, 2] - p[:, 0]
+            pvec = cross(d[m], e2)
+            det = dot(e1, pvec)
+            inv = f32(1) / det
+            tvec = o[m] - p0
+            uu = dot(tvec, pvec) * inv
+            qvec = cross(tvec, e1)
+            vv = dot(d[m], qvec) * inv
+            tt = dot(e2, qvec) * inv
+            ok = (~((det > f32(-1e-8)) & (det < f32(1e-8))) & ~((uu < 0) | (uu > 1)) & ~((vv < 0) | (uu + vv > 1))
+                  & (tt >= mint[m]) & (tt <= maxt[m]))
+            hit[m], t[m], u[m], v[m] = ok, tt, uu, vv
+        m = np.flatnonzero(sphere)
+        if m.size:
+            cen = np.array([list(sh.center) for sh in shapes], f32)[shape[m]]
+            rad = np.array([sh.radius for sh in shapes], f32)[shape[m]]
+            oc = o[m] - cen
+            A = dot(d[m], d[m])
+            B = f32(2) * dot(oc, d[m])
+            Cc = dot(oc, oc) - rad * rad
+            disc = B * B - f32(4) * A * Cc
+            delta = np.sqrt(disc)
+            t1, t2 = (-B - delta) / (f32(2) * A), (-B + delta) / (f32(2) * A)
+            in1 = (mint[m] <= t1) & (t1 <= maxt[m])
+            in2 = (mint[m] <= t2) & (t2 <= maxt[m])
+            hit[m] = (disc > 0) & (in1 | in2)
+            t[m] = np.where(in1, t1, t2)
+    t[~hit] = np.inf
+    return hit, t, u, v
+
+
 # Image parity against the oracle on identical WAVE streams (tests/test_gpu_*.py).
 # BASELINE.json's bar is per-pixel L2 < 1e-3; the tests assert what the code
 # achieves.  Transcendentals differ by a few ulp between the ROCm device

@@ -80,7 +80,7 @@ def test_c3_size_trace_matches_oracle(c3):
     print("C3 BVH:", nori_amd.bvh_info(s))
     rays = np.concatenate([_rays(30000, 11, [-0.9, 0.05, -0.9], [0.9, 1.5, 0.9]),
                            _rays(5000, 12, [-3, -1, -3], [3, 3, 6], mint=0.01)])
-    _compare_hits(r.trace(rays), o.trace(rays))
+    print("id mismatches, all ties:", _compare_hits(r.trace(rays), o.trace(rays), s, rays))
     sh = rays.copy()
     sh[:, 7] = np.random.default_rng(13).uniform(0.01, 2.0, size=sh.shape[0])
     assert ((r.trace(sh, any_hit=True)["prim"] >= 0) == (o.trace(sh, any_hit=True)["prim"] >= 0)).all()
