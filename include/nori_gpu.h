@@ -42,6 +42,10 @@
  *   nori_scene_bvh_info   <- BVH::build/statistics        src/bvh.cpp:329-402
  *   nori_scene_scan_list  (introspection: the small-scene scan list and its
  *                          exact in-plane filters, for the CPU tests)
+ *   nori_gpu_update_vertices, nori_scene_bvh_refit, nori_gpu_bvh_read
+ *                         (dynamic geometry: new vertex positions and a BVH
+ *                          refit on the device; no reference counterpart, the
+ *                          reference builds its BVH once in Scene::activate)
  *   nori_gpu_comm_*, nori_gpu_render_sharded
  *                         <- the same pass loop spread over the GPUs of a node,
  *                            one process per GPU; the cross-GPU film merge is
@@ -600,6 +604,99 @@ int nori_gpu_query(nori_gpu_ctx *ctx, const nori_gpu_query_desc *desc, const flo
  * rays: pass_count x H x W x 8 floats.  Works on a context of any integrator.
  * Blocking, on the context's stream. */
 int nori_gpu_camera_rays(nori_gpu_ctx *ctx, const nori_gpu_render_desc *desc, float *rays);
+
+/* ---- dynamic geometry: new vertex positions, the BVH refitted on the device ----
+ * (no reference counterpart: the reference builds its BVH once, in
+ * Scene::activate; deviation D14) */
+typedef struct nori_gpu_update_desc {
+    const float *positions;  /* num_vertices x 3 floats, required                              */
+    const float *normals;    /* num_vertices x 3 floats, or NULL: the vertex normals stay      */
+    uint32_t num_vertices;   /* must equal the scene's num_vertices                            */
+    int32_t  on_device;      /* both pointers are device memory on the context's device        */
+    uint32_t reserved[4];    /* must be 0 */
+} nori_gpu_update_desc;
+typedef struct nori_gpu_update_stats {
+    float ms;                /* wall time of the call (host timer)                              */
+    float ms_device;         /* HIP-event time of the vertex, record and refit launches         */
+    float root_min[3], root_max[3];  /* the scene box after the refit                          */
+    uint32_t nodes;          /* 4-wide nodes refitted                                           */
+    uint32_t levels;         /* refit launches (the levels of the schedule)                     */
+    uint32_t launches;       /* kernel launches of the call in all                              */
+    uint32_t reserved;
+} nori_gpu_update_stats;
+
+/* The refit's one statement, on the host (no device needed); the kernels of
+ * nori_gpu_update_vertices are tested against it byte for byte.  Builds the
+ * scene's device BVH exactly as nori_gpu_create does (node and primitive
+ * counts: nori_scene_bvh_info's device_nodes and num_prims) and refits it to
+ * `positions` (num_vertices x 3 floats; NULL: the tree as built, nothing
+ * refitted):
+ *   - topology, child refs, leaf ranges and leaf order do not change;
+ *   - a triangle's record becomes (p0 | id), (p1 - p0 | w), (p2 - p0 | w) with
+ *     p0, p1, p2 its vertices' new positions and every w word as it was; a
+ *     sphere's record stays (spheres do not move: centre and radius belong to
+ *     the shape);
+ *   - the box of a leaf child is the component-wise min / max of the vertex
+ *     POSITIONS of its triangles (not of v0 + e1, which can differ by an ulp)
+ *     and of centre -/+ radius of its spheres; the box of an inner child is
+ *     the min / max over the used slots of that child node;
+ *   - an unused child slot is the one whose box is NaN (its ref, the leaf bit
+ *     alone, is also the valid ref of a one-primitive leaf at record 0); it is
+ *     never written and stays NaN;
+ *   - min and max order the zeros, -0 < +0, so a box depends on the set of its
+ *     points only; they do not round: any correct implementation gives the
+ *     same bytes.
+ * nodes: 32 floats per node, prims: 12 floats per primitive record (the
+ * layouts of nori_gpu_bvh_read), root_box: min.xyz, max.xyz over the root
+ * node's used slots -- the min / max over all primitives; each may be NULL.
+ * The statement has no memory: the result depends on the scene and on
+ * `positions` only.  NORI_ERR_INVALID: a null scene, a non-finite position. */
+int nori_scene_bvh_refit(const nori_scene_desc *scene, const float *positions, float *nodes, float *prims,
+                         float root_box[6]);
+
+/* Moves the context's mesh vertices to desc->positions (and, if given, sets
+ * their normals) and refits the BVH as nori_scene_bvh_refit states, all on the
+ * device: pos.xyz / nrm.xyz are rewritten (their w lanes, the texture
+ * coordinates, stay), the triangle records rebuilt, the boxes refitted level
+ * by level (one launch per level of a schedule made at nori_gpu_create), and
+ * what the lights derive from the geometry recomputed -- for every mesh that
+ * carries an emitter the area CDF and its normalisation, in
+ * nori_gpu_create's own fp32 order (on the host, from a read-back of those
+ * meshes' vertices: a refitted context samples its lights bit-identically to
+ * a fresh one on the same positions).  The CDF of a mesh without an emitter
+ * is read by no kernel and goes stale.  The scene box becomes the refitted
+ * root box.  Every sphere's `solitary` shortcut (an exact shortcut of the
+ * tail finisher whose precondition, no other primitive near the ball, was
+ * checked against the geometry as loaded) is switched off for good.  Every
+ * later render, feature pass, trace and query of the context sees the new
+ * geometry; hit distances and barycentrics are those of a context created
+ * fresh on the same positions, bit for bit (they depend on the triangle
+ * record alone), at the traversal cost of a tree whose topology was chosen
+ * for the old positions.
+ * Host arrays are staged through context-owned device buffers; with on_device
+ * the pointers are used in place (4-byte aligned; the caller has made them
+ * ready before the call) and nothing is copied.  Blocking; runs on the
+ * context's stream: concurrent use with a render or query of the same context
+ * is not supported.  The host nori_scene is not touched: nori_scene_surface,
+ * nori_scene_bvh_refit(.., NULL, ..) and the scene's arrays keep describing
+ * the geometry as loaded.
+ * Refused with nothing changed (the context renders exactly as before):
+ * NORI_ERR_UNSUPPORTED -- a scan-mode context (its scan list, axis-plane
+ *   pairs and specialised kernels are functions of the geometry: create the
+ *   context with NORI_TRAVERSAL=bvh), a photonmapper context (its photon map
+ *   was traced at creation);
+ * NORI_ERR_INVALID -- a null ctx, desc or positions, num_vertices other than
+ *   the scene's, reserved != 0, an on_device pointer that is not 4-byte
+ *   aligned or that the HIP runtime does not know as device memory, any non-finite position or normal (counted on the device in a
+ *   pass of its own before anything is modified, device buffers included).
+ * stats may be NULL. */
+int nori_gpu_update_vertices(nori_gpu_ctx *ctx, const nori_gpu_update_desc *desc, nori_gpu_update_stats *stats);
+/* Introspection for tests, like nori_scene_scan_list: the context's BVH nodes
+ * (32 floats per node) and primitive records (12 floats per record, leaf
+ * order; a scan-mode context holds its scan list there) as they are on the
+ * device.  counts (may be NULL) receives the node and record counts; nodes and
+ * prims may each be NULL (call with both NULL for the counts).  Blocking. */
+int nori_gpu_bvh_read(nori_gpu_ctx *ctx, float *nodes, float *prims, uint32_t counts[2]);
 int nori_gpu_cancel(nori_gpu_ctx *ctx);
 float nori_gpu_progress(const nori_gpu_ctx *ctx);
 void nori_gpu_destroy(nori_gpu_ctx *ctx);

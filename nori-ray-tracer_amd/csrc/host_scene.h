@@ -85,6 +85,30 @@ struct DeviceBvh {
 // Binned-SAH build with the reference's algorithm (bvh.cpp:100-382).
 void build_device_bvh(const nori_scene_desc &d, const float root_min[3], const float root_max[3], DeviceBvh &out);
 
+// ---- BVH refit (bvh_refit.cpp; stated at nori_scene_bvh_refit in nori_gpu.h)
+// The order in which a refit recomputes the child boxes: `slots` holds
+// 4 * node + child slot of every USED slot (an unused slot has a NaN box and
+// is never written), level 0 = the leaf slots, level h >= 1 = the inner slots
+// of the nodes of height h (the longest way down to a node without inner
+// children).  A slot of level h reads only boxes that levels < h wrote, so
+// the device runs one launch per level.  Level l is slots[level_begin[l] ..
+// level_begin[l + 1]).
+struct RefitPlan {
+    std::vector<uint32_t> slots;
+    std::vector<uint32_t> level_begin;
+    uint32_t levels() const { return (uint32_t)level_begin.size() - 1; }
+};
+RefitPlan build_refit_plan(const DeviceBvh &bvh);
+// Vertex ids of every global primitive (shape order; a sphere takes 0, 0, 0);
+// throws on an index outside the scene.
+std::vector<uint32_t> prim_vertex_ids(const nori_scene_desc &d);
+// Rewrites the triangle records and refits the boxes of `bvh` to `positions`
+// (3 floats per vertex, finite); root_box (may be null): min, max over the
+// root's used slots.
+void refit_host(DeviceBvh &bvh, const RefitPlan &plan, const std::vector<uint32_t> &vidx, const float *positions,
+                float root_box[6]);
+void refit_root_box(const float *root_node, float box[6]);
+
 // Photon map (photon_map.cpp): raw = n photons x 12 floats (position, 0,
 // direction towards the light, 0, power, 0) in emission order -> photons as
 // (x, y, z, theta | phi << 8) and RGBE words (the reference's PhotonData),

@@ -155,5 +155,18 @@ hipError_t launch_block_error(const float *stats, int W, int H, int nbx, const u
                               float *err, hipStream_t st);
 // dst[i] += src[i], i < n (device buffers)
 hipError_t launch_add_into(float *dst, const float *src, size_t n, hipStream_t st);
+// Dynamic geometry (refit.hip; the refit is stated at nori_scene_bvh_refit in
+// nori_gpu.h).  All pointers are device memory.
+// *count += the non-finite values among a[0 .. n) and, if given, b[0 .. n).
+hipError_t launch_refit_count_nonfinite(const float *a, const float *b, size_t n, uint32_t *count, hipStream_t st);
+// pos[v].xyz = p[3v ..] and, if n is given, nrm[v].xyz = n[3v ..], v < V; the w lanes stay.
+hipError_t launch_refit_set_vertices(float4 *pos, float4 *nrm, const float *p, const float *n, uint32_t V,
+                                     hipStream_t st);
+// The P leaf-order records rebuilt from pos through vidx (spheres left alone).
+hipError_t launch_refit_records(float4 *prims, const uint32_t *vidx, const float4 *pos, uint32_t P, hipStream_t st);
+// One level of the refit schedule (RefitPlan, host_scene.h): the boxes of the n
+// (node, slot) entries of `slots`; the levels below have completed on `st`.
+hipError_t launch_refit_level(float4 *nodes, const float4 *prims, const uint32_t *vidx, const float4 *pos,
+                              const uint32_t *slots, uint32_t n, hipStream_t st);
 
 }  // namespace nori

@@ -237,6 +237,19 @@ struct nori_gpu_ctx {
     DevBuf q_rays, q_hits, q_surf;
     hipEvent_t q_ev[3] = {};
     DevBuf ph, ph_rgbe, ph_tab, ph_start;             // photonmapper: photon map (photon_map.cpp) and its hash-grid buckets
+    // nori_gpu_update_vertices: the refit schedule (host copy of its level bounds, device copy of
+    // its slots), staging of host positions / normals, the non-finite counter, the shapes as
+    // uploaded (area_norm and solitary change) and the meshes that carry an emitter
+    RefitPlan refit;
+    DevBuf refit_slots, upd_pos, upd_nrm, upd_count;
+    hipEvent_t upd_ev[2] = {};
+    uint32_t num_vertices = 0;
+    std::vector<DevShape> hshapes;
+    struct EmitterMesh {
+        uint32_t shape, cdf_offset, vtx_first, vtx_count;  // the vertex range its triangles use
+        std::vector<uint32_t> tri;                          // 3 global vertex ids per triangle
+    };
+    std::vector<EmitterMesh> emitter_meshes;
     uint32_t pool_cap = 0;
     uint32_t *pinned = nullptr;      // host-mapped flags: [0] done, [1] exhausted segments
     uint32_t *pinned_dev = nullptr;  // device view of `pinned`
@@ -259,6 +272,8 @@ struct nori_gpu_ctx {
         }
         scan_rtc_release(rtc);
         for (auto e : q_ev)
+            if (e) (void)hipEventDestroy(e);
+        for (auto e : upd_ev)
             if (e) (void)hipEventDestroy(e);
         if (pinned) (void)hipHostFree(pinned);
         if (readback) (void)hipHostFree(readback);
@@ -624,6 +639,30 @@ bool basic_scene(const nori_scene_desc &d) {
     return d.camera.camera_type == NORI_CAMERA_PERSPECTIVE;
 }
 
+// Mesh::activate's area DiscretePDF (mesh.cpp:30-38, dpdf.h:58-91) of a mesh
+// whose triangle t has the vertices tri[3t .. 3t+2] of vtx(id): the serial
+// fp32 running sum of the areas, times 1 / sum, last entry 1, in cdf (count + 1
+// entries).  Returns DiscretePDF::getNormalization = 1 / sum, 0 for a mesh
+// without area (its CDF stays unnormalised).  The one statement of both
+// nori_gpu_create and nori_gpu_update_vertices.
+template <class Vtx> float mesh_area_cdf(const uint32_t *tri, uint32_t count, Vtx vtx, std::vector<float> &cdf) {
+    cdf.assign((size_t)count + 1, 0.0f);
+    for (uint32_t t = 0; t < count; ++t) {
+        const uint32_t *f = tri + 3 * (size_t)t;
+        const float *p0 = vtx(f[0]), *p1 = vtx(f[1]), *p2 = vtx(f[2]);
+        float e1[3] = {p1[0] - p0[0], p1[1] - p0[1], p1[2] - p0[2]}, e2[3] = {p2[0] - p0[0], p2[1] - p0[1], p2[2] - p0[2]};
+        float cx = e1[1] * e2[2] - e1[2] * e2[1], cy = e1[2] * e2[0] - e1[0] * e2[2], cz = e1[0] * e2[1] - e1[1] * e2[0];
+        float area = 0.5f * std::sqrt((cx * cx + cy * cy) + cz * cz);
+        cdf[t + 1] = cdf[t] + area;
+    }
+    const float sum = cdf[count];
+    if (!(sum > 0)) return 0.0f;
+    const float norm = 1.0f / sum;
+    for (uint32_t t = 1; t <= count; ++t) cdf[t] *= norm;
+    cdf[count] = 1.0f;
+    return norm;
+}
+
 void upload_scene(nori_gpu_ctx &c, const nori_scene_desc &d) {
     float rmin[3] = {__builtin_inff(), __builtin_inff(), __builtin_inff()};
     float rmax[3] = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
@@ -659,6 +698,7 @@ void upload_scene(nori_gpu_ctx &c, const nori_scene_desc &d) {
     std::vector<DevShape> shapes(d.num_shapes);
     std::vector<uint32_t> prim_shape, tri_vidx;
     std::vector<float> cdf;
+    std::vector<nori_gpu_ctx::EmitterMesh> emitter_meshes;
     uint32_t off = 0;
     for (uint32_t s = 0; s < d.num_shapes; ++s) {
         const nori_shape_desc &sd = d.shapes[s];
@@ -692,31 +732,27 @@ void upload_scene(nori_gpu_ctx &c, const nori_scene_desc &d) {
                 throw NoriException(NORI_ERR_INVALID, "mesh range outside the scene arrays");
             ds.prim_count = sd.tri_count;
             ds.cdf_offset = (uint32_t)cdf.size();
-            // Mesh::activate area DiscretePDF (mesh.cpp:30-38, dpdf.h:58-91)
-            std::vector<float> c(sd.tri_count + 1);
-            c[0] = 0.0f;
             for (uint32_t t = 0; t < sd.tri_count; ++t) {
                 const uint32_t *f = d.indices + 3 * (size_t)(sd.tri_offset + t);
                 for (int k = 0; k < 3; ++k)
                     if (f[k] >= d.num_vertices) throw NoriException(NORI_ERR_INVALID, "vertex index out of range");
-                const float *p0 = d.positions + 3 * (size_t)f[0], *p1 = d.positions + 3 * (size_t)f[1], *p2 = d.positions + 3 * (size_t)f[2];
-                float e1[3] = {p1[0] - p0[0], p1[1] - p0[1], p1[2] - p0[2]}, e2[3] = {p2[0] - p0[0], p2[1] - p0[1], p2[2] - p0[2]};
-                float cx = e1[1] * e2[2] - e1[2] * e2[1], cy = e1[2] * e2[0] - e1[0] * e2[2], cz = e1[0] * e2[1] - e1[1] * e2[0];
-                float area = 0.5f * std::sqrt((cx * cx + cy * cy) + cz * cz);
-                c[t + 1] = c[t] + area;
                 prim_shape.push_back(s);
                 tri_vidx.insert(tri_vidx.end(), {f[0], f[1], f[2]});
             }
-            float sum = c[sd.tri_count];
-            if (sum > 0) {
-                float norm = 1.0f / sum;
-                for (uint32_t t = 1; t <= sd.tri_count; ++t) c[t] *= norm;
-                c[sd.tri_count] = 1.0f;
-                ds.area_norm = norm;
-            } else {
-                ds.area_norm = 0.0f;
+            std::vector<float> mc;
+            const uint32_t *tri = d.indices + 3 * (size_t)sd.tri_offset;
+            ds.area_norm = mesh_area_cdf(tri, sd.tri_count, [&](uint32_t i) { return d.positions + 3 * (size_t)i; }, mc);
+            cdf.insert(cdf.end(), mc.begin(), mc.end());
+            if (sd.emitter >= 0 && sd.tri_count) {  // nori_gpu_update_vertices recomputes this mesh's CDF
+                nori_gpu_ctx::EmitterMesh em;
+                em.shape = s;
+                em.cdf_offset = ds.cdf_offset;
+                em.tri.assign(tri, tri + 3 * (size_t)sd.tri_count);
+                const auto mm = std::minmax_element(em.tri.begin(), em.tri.end());
+                em.vtx_first = *mm.first;
+                em.vtx_count = *mm.second - *mm.first + 1;
+                emitter_meshes.push_back(std::move(em));
             }
-            cdf.insert(cdf.end(), c.begin(), c.end());
             for (uint32_t v = 0; v < sd.vtx_count; ++v) {
                 const float *p = d.positions + 3 * (size_t)(sd.vtx_offset + v);
                 expand(p[0], p[1], p[2]);
@@ -866,6 +902,14 @@ void upload_scene(nori_gpu_ctx &c, const nori_scene_desc &d) {
     if (env.empty()) env.assign(4, 0.0f);
     c.env.upload(env);
     c.scene_bytes = c.nodes.bytes + c.prims.bytes;
+    // nori_gpu_update_vertices (BVH contexts): the order in which a refit recomputes the boxes
+    c.hshapes = shapes;
+    c.emitter_meshes = std::move(emitter_meshes);
+    c.num_vertices = d.num_vertices;
+    if (!scan) {
+        c.refit = build_refit_plan(bvh);
+        c.refit_slots.upload(c.refit.slots);
+    }
     // small-scene blob (staged into LDS by the tail finisher)
     std::vector<char> blob;
     uint32_t offs[10] = {0};
@@ -1823,6 +1867,130 @@ int camera_rays(nori_gpu_ctx &c, const nori_gpu_render_desc &rd, float *rays) {
     return NORI_OK;
 }
 
+// nori_gpu_update_vertices (stated in nori_gpu.h): validate, then on the
+// context's stream count the non-finite inputs (nothing is modified before
+// that count is back), set the vertices, rebuild the records, refit the boxes
+// one launch per level of c.refit, and bring the lights and the scene box up
+// to date.
+int update_vertices(nori_gpu_ctx &c, const nori_gpu_update_desc &ud, nori_gpu_update_stats *stats) {
+    const auto t0 = std::chrono::steady_clock::now();
+    if (c.stack == 0)
+        throw NoriException(NORI_ERR_UNSUPPORTED,
+                            "nori_gpu_update_vertices: a scan-mode context (its scan list and specialised kernels "
+                            "are functions of the geometry); create the context with NORI_TRAVERSAL=bvh");
+    if (c.S.integrator == NORI_INTEGRATOR_PHOTONMAPPER)
+        throw NoriException(NORI_ERR_UNSUPPORTED,
+                            "nori_gpu_update_vertices: a photonmapper context (its photon map was traced at creation)");
+    if (ud.num_vertices != c.num_vertices)
+        throw NoriException(NORI_ERR_INVALID, "nori_gpu_update_vertices: num_vertices " + std::to_string(ud.num_vertices) +
+                                                  " is not the scene's " + std::to_string(c.num_vertices));
+    for (uint32_t r : ud.reserved)
+        if (r != 0) throw NoriException(NORI_ERR_INVALID, "nori_gpu_update_vertices: reserved must be 0");
+    if (ud.on_device && ((uintptr_t)ud.positions % 4 || (uintptr_t)ud.normals % 4))
+        throw NoriException(NORI_ERR_INVALID, "nori_gpu_update_vertices: device pointers must be 4-byte aligned");
+    HIP_TRY(hipSetDevice(c.device));
+    if (ud.on_device)  // a host pointer here would fault in the first kernel: ask the runtime what it is
+        for (const float *p : {ud.positions, ud.normals}) {
+            hipPointerAttribute_t at{};
+            if (!p) continue;
+            if (hipPointerGetAttributes(&at, p) != hipSuccess ||
+                (at.type != hipMemoryTypeDevice && at.type != hipMemoryTypeManaged)) {
+                (void)hipGetLastError();
+                throw NoriException(NORI_ERR_INVALID, "nori_gpu_update_vertices: on_device with a pointer that is not device memory");
+            }
+        }
+    for (auto &e : c.upd_ev)
+        if (!e) HIP_TRY(hipEventCreate(&e));
+    const uint32_t V = c.num_vertices;
+    const size_t nfl = 3 * (size_t)V;
+    const float *dp = ud.positions, *dn = ud.normals;
+    if (!ud.on_device) {
+        c.upd_pos.ensure(nfl * 4);
+        HIP_TRY(hipMemcpyAsync(c.upd_pos.p, ud.positions, nfl * 4, hipMemcpyHostToDevice, c.stream));
+        dp = c.upd_pos.as<float>();
+        if (ud.normals) {
+            c.upd_nrm.ensure(nfl * 4);
+            HIP_TRY(hipMemcpyAsync(c.upd_nrm.p, ud.normals, nfl * 4, hipMemcpyHostToDevice, c.stream));
+            dn = c.upd_nrm.as<float>();
+        }
+    }
+    uint32_t launches = 0;
+    // ---- a pass of its own: nothing is modified before its count is back
+    c.upd_count.ensure(4);
+    HIP_TRY(hipMemsetAsync(c.upd_count.p, 0, 4, c.stream));
+    HIP_TRY(launch_refit_count_nonfinite(dp, dn, nfl, c.upd_count.as<uint32_t>(), c.stream));
+    ++launches;
+    uint32_t bad = 0;
+    HIP_TRY(hipMemcpyAsync(&bad, c.upd_count.p, 4, hipMemcpyDeviceToHost, c.stream));
+    HIP_TRY(hipStreamSynchronize(c.stream));
+    if (bad)
+        throw NoriException(NORI_ERR_INVALID, "nori_gpu_update_vertices: " + std::to_string(bad) +
+                                                  " non-finite position or normal values; nothing was changed");
+    // ---- vertices, records, boxes
+    float4 *pos = c.pos.as<float4>();
+    HIP_TRY(hipEventRecord(c.upd_ev[0], c.stream));
+    HIP_TRY(launch_refit_set_vertices(pos, c.nrm.as<float4>(), dp, dn, V, c.stream));
+    HIP_TRY(launch_refit_records(c.prims.as<float4>(), c.S.tri_vidx, pos, c.S.num_prims, c.stream));
+    launches += 2;
+    for (uint32_t l = 0; l < c.refit.levels(); ++l) {
+        const uint32_t b = c.refit.level_begin[l], n = c.refit.level_begin[l + 1] - b;
+        HIP_TRY(launch_refit_level(c.nodes.as<float4>(), c.S.prims, c.S.tri_vidx, pos, c.refit_slots.as<uint32_t>() + b, n,
+                                   c.stream));
+        launches += n ? 1u : 0u;
+    }
+    HIP_TRY(hipEventRecord(c.upd_ev[1], c.stream));
+    // ---- the scene box: the root node's used slots (128 bytes back)
+    float root[32], box[6];
+    HIP_TRY(hipMemcpyAsync(root, c.nodes.p, sizeof(root), hipMemcpyDeviceToHost, c.stream));
+    // ---- the lights: area CDF and normalisation of every mesh with an emitter, in nori_gpu_create's
+    // own order on the host (mesh_area_cdf) from a read-back of that mesh's vertices; emitter meshes are small
+    std::vector<std::vector<float>> verts(c.emitter_meshes.size());
+    for (size_t m = 0; m < c.emitter_meshes.size(); ++m) {
+        const auto &em = c.emitter_meshes[m];
+        verts[m].resize(4 * (size_t)em.vtx_count);
+        HIP_TRY(hipMemcpyAsync(verts[m].data(), pos + em.vtx_first, 16 * (size_t)em.vtx_count, hipMemcpyDeviceToHost,
+                               c.stream));
+    }
+    HIP_TRY(hipStreamSynchronize(c.stream));
+    refit_root_box(root, box);
+    for (size_t m = 0; m < c.emitter_meshes.size(); ++m) {
+        const auto &em = c.emitter_meshes[m];
+        std::vector<float> cdf;
+        const float *v = verts[m].data();
+        c.hshapes[em.shape].area_norm = mesh_area_cdf(em.tri.data(), (uint32_t)(em.tri.size() / 3),
+                                                      [&](uint32_t i) { return v + 4 * (size_t)(i - em.vtx_first); }, cdf);
+        HIP_TRY(hipMemcpyAsync(c.cdf.as<float>() + em.cdf_offset, cdf.data(), cdf.size() * 4, hipMemcpyHostToDevice,
+                               c.stream));
+        HIP_TRY(hipStreamSynchronize(c.stream));  // (cdf is a local)
+    }
+    // the solitary shortcut's precondition was checked against the geometry as loaded: off for good
+    for (DevShape &sh : c.hshapes)
+        if (sh.type == NORI_SHAPE_SPHERE) sh.solitary = 0;
+    HIP_TRY(hipMemcpyAsync(c.shapes.p, c.hshapes.data(), c.hshapes.size() * sizeof(DevShape), hipMemcpyHostToDevice,
+                           c.stream));
+    HIP_TRY(hipStreamSynchronize(c.stream));
+    for (int k = 0; k < 3; ++k) c.S.root_min[k] = box[k], c.S.root_max[k] = box[3 + k];
+    if (stats) {
+        std::memset(stats, 0, sizeof(*stats));
+        HIP_TRY(hipEventElapsedTime(&stats->ms_device, c.upd_ev[0], c.upd_ev[1]));
+        for (int k = 0; k < 3; ++k) stats->root_min[k] = box[k], stats->root_max[k] = box[3 + k];
+        stats->nodes = c.bvh_nodes;
+        stats->levels = c.refit.levels();
+        stats->launches = launches;
+        stats->ms = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+    return NORI_OK;
+}
+
+int bvh_read(nori_gpu_ctx &c, float *nodes, float *prims, uint32_t *counts) {
+    HIP_TRY(hipSetDevice(c.device));
+    if (counts) counts[0] = c.S.num_nodes, counts[1] = c.S.num_prims;
+    HIP_TRY(hipStreamSynchronize(c.stream));
+    if (nodes) HIP_TRY(hipMemcpy(nodes, c.nodes.p, 128 * (size_t)c.S.num_nodes, hipMemcpyDeviceToHost));
+    if (prims) HIP_TRY(hipMemcpy(prims, c.prims.p, 48 * (size_t)c.S.num_prims, hipMemcpyDeviceToHost));
+    return NORI_OK;
+}
+
 int frame_blocks(const nori_gpu_ctx &c, int *nbx_out = nullptr) {
     const int nbx = (c.S.W + NORI_BLOCK_SIZE - 1) / NORI_BLOCK_SIZE, nby = (c.S.H + NORI_BLOCK_SIZE - 1) / NORI_BLOCK_SIZE;
     if (nbx_out) *nbx_out = nbx;
@@ -2376,6 +2544,39 @@ int nori_gpu_camera_rays(nori_gpu_ctx *c, const nori_gpu_render_desc *rd, float 
         if (!c || !rd || !rays) return fail(NORI_ERR_INVALID, "null argument");
         if (rd->num_blocks && !rd->block_ids) return fail(NORI_ERR_INVALID, "block_ids is null");
         return camera_rays(*c, *rd, rays);
+    });
+}
+
+int nori_gpu_update_vertices(nori_gpu_ctx *c, const nori_gpu_update_desc *ud, nori_gpu_update_stats *stats) {
+    return guarded([&] {
+        if (!c || !ud || !ud->positions) return fail(NORI_ERR_INVALID, "null argument");
+        return update_vertices(*c, *ud, stats);
+    });
+}
+
+int nori_gpu_bvh_read(nori_gpu_ctx *c, float *nodes, float *prims, uint32_t *counts) {
+    return guarded([&] {
+        if (!c) return fail(NORI_ERR_INVALID, "null argument");
+        return bvh_read(*c, nodes, prims, counts);
+    });
+}
+
+int nori_scene_bvh_refit(const nori_scene_desc *d, const float *positions, float *nodes, float *prims, float *root_box) {
+    return guarded([&] {
+        if (!d) return fail(NORI_ERR_INVALID, "null argument");
+        if (d->abi_version != NORI_GPU_ABI_VERSION) return fail(NORI_ERR_INVALID, "ABI version mismatch");
+        if (positions)
+            for (size_t i = 0; i < 3 * (size_t)d->num_vertices; ++i)
+                if (!std::isfinite(positions[i])) return fail(NORI_ERR_INVALID, "nori_scene_bvh_refit: a non-finite position");
+        float rmin[3], rmax[3];
+        scene_root_box(*d, rmin, rmax);
+        DeviceBvh bvh;
+        build_device_bvh(*d, rmin, rmax, bvh);
+        if (positions) refit_host(bvh, build_refit_plan(bvh), prim_vertex_ids(*d), positions, nullptr);
+        if (nodes) std::memcpy(nodes, bvh.nodes.data(), bvh.nodes.size() * 4);
+        if (prims) std::memcpy(prims, bvh.prims.data(), bvh.prims.size() * 4);
+        if (root_box) refit_root_box(bvh.nodes.data(), root_box);
+        return NORI_OK;
     });
 }
 

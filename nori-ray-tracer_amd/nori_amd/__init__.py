@@ -27,7 +27,7 @@ from ._abi import NoriError, check, lib  # noqa: F401
 __all__ = ["load_scene", "Scene", "GpuRenderer", "RenderThread", "NoriError", "device_count",
            "develop", "write_exr", "write_png", "read_exr", "film_variance", "ldr_bytes", "variance_gray",
            "denoise", "read_image", "block_error", "film_features", "denoise_guided", "film_denoise_guided",
-           "scene_surface"]
+           "scene_surface", "bvh_refit"]
 
 
 def _fptr(a):
@@ -299,6 +299,25 @@ def bvh_info(scene):
     info = BvhInfo()
     check(lib().nori_scene_bvh_info(scene.desc_ptr, C.byref(info)))
     return {k: getattr(info, k) for k, _ in BvhInfo._fields_ if k != "pad"}
+
+
+def bvh_refit(scene, positions=None):
+    """The scene's device BVH as GpuRenderer builds it, refitted to `positions` ((num_vertices, 3)
+    float32; None: the tree as built) on the host -- nori_scene_bvh_refit, where the refit is stated;
+    no GPU needed.  Returns (nodes (n, 32), prims (p, 12), root_box (6,)) as float32: the arrays
+    GpuRenderer.bvh_nodes() returns after update_vertices(positions), byte for byte."""
+    info = bvh_info(scene)
+    nodes = np.zeros((info["device_nodes"], 32), np.float32)
+    prims = np.zeros((info["num_prims"], 12), np.float32)
+    box = np.zeros(6, np.float32)
+    p = None
+    if positions is not None:
+        p = np.ascontiguousarray(positions, dtype=np.float32)
+        if p.shape != (scene.desc.num_vertices, 3):
+            raise ValueError(f"positions {p.shape}: expected {(scene.desc.num_vertices, 3)}")
+    check(lib().nori_scene_bvh_refit(scene.desc_ptr, None if p is None else _fptr(p), _fptr(nodes), _fptr(prims),
+                                     _fptr(box)))
+    return nodes, prims, box
 
 
 class ScanInfo(C.Structure):
@@ -574,6 +593,64 @@ class GpuRenderer:
         assert out.dtype == np.float32 and out.flags.c_contiguous and out.shape == shape
         check(lib().nori_gpu_camera_rays(self._h, C.byref(rd), C.c_void_p(out.ctypes.data)))
         return out
+
+    def _vertex_arg(self, a, what):
+        """(address, on_device, keep-alive) of a positions / normals argument of update_vertices."""
+        n = self.scene.desc.num_vertices
+        if isinstance(a, np.ndarray):
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            if a.shape != (n, 3):
+                raise ValueError(f"{what} {a.shape}: expected {(n, 3)}")
+            return a.ctypes.data, 0, a
+        if hasattr(a, "data_ptr"):  # a torch tensor: used in place, no host copy
+            if not a.is_cuda or a.device.index != self.device:
+                raise ValueError(f"{what}: a tensor on {a.device}, the context is on device {self.device}")
+            if tuple(a.shape) != (n, 3) or "float32" not in str(a.dtype) or not a.is_contiguous():
+                raise ValueError(f"{what}: expected a contiguous float32 tensor of shape {(n, 3)}")
+            return a.data_ptr(), 1, a
+        return int(a), 1, None  # an int device address of n x 3 floats
+
+    def update_vertices(self, positions, normals=None):
+        """Move the scene's mesh vertices and refit the BVH on the device (nori_gpu_update_vertices):
+        every later render, features, trace and query of this context sees the new geometry.
+
+        positions, normals (optional: the vertex normals stay): (num_vertices, 3) float32 numpy
+        arrays, or torch tensors on the context's device (used in place: no host copy; work queued
+        on them is waited for first), or int device addresses (the caller has made them ready).
+        Both must be of the same kind.  Spheres do not move, the topology stays, and `self.scene`
+        keeps describing the geometry as loaded.  Scan-mode contexts (create with
+        NORI_TRAVERSAL=bvh) and photonmapper contexts raise NoriError (unsupported); non-finite
+        values raise NoriError (invalid) with nothing changed.  Returns the stats as a dict: ms,
+        ms_device, root_min, root_max, nodes, levels, launches."""
+        ud = _abi.UpdateDesc()
+        p, dev, keep_p = self._vertex_arg(positions, "positions")
+        ud.positions, ud.on_device = p, dev
+        keep_n = None
+        if normals is not None:
+            q, dev_n, keep_n = self._vertex_arg(normals, "normals")
+            if dev_n != dev:
+                raise ValueError("positions and normals must both be host arrays or both be device buffers")
+            ud.normals = q
+        ud.num_vertices = self.scene.desc.num_vertices
+        if dev and (hasattr(positions, "data_ptr") or hasattr(normals, "data_ptr")):
+            import torch  # (the caller's: a tensor was passed)
+
+            torch.cuda.synchronize(self.device)
+        st = _abi.UpdateStats()
+        check(lib().nori_gpu_update_vertices(self._h, C.byref(ud), C.byref(st)))
+        del keep_p, keep_n
+        return st.as_dict()
+
+    def bvh_nodes(self):
+        """The context's BVH as it is on the device (nori_gpu_bvh_read; introspection for tests):
+        (nodes (n, 32), prims (p, 12)) float32 -- 4-wide nodes and leaf-order primitive records
+        (a scan-mode context holds its scan list in prims)."""
+        counts = (C.c_uint32 * 2)()
+        check(lib().nori_gpu_bvh_read(self._h, None, None, counts))
+        nodes = np.zeros((counts[0], 32), np.float32)
+        prims = np.zeros((counts[1], 12), np.float32)
+        check(lib().nori_gpu_bvh_read(self._h, _fptr(nodes), _fptr(prims), counts))
+        return nodes, prims
 
     def cancel(self):
         check(lib().nori_gpu_cancel(self._h))

@@ -138,6 +138,22 @@ class QueryDesc(C.Structure):
     _fields_ = [("n", C.c_uint32), ("any_hit", C.c_int32), ("on_device", C.c_int32), ("reserved", C.c_uint32)]
 
 
+class UpdateDesc(C.Structure):
+    """nori_gpu_update_desc: new vertex positions (and normals) for nori_gpu_update_vertices."""
+    _fields_ = [("positions", C.c_void_p), ("normals", C.c_void_p), ("num_vertices", C.c_uint32),
+                ("on_device", C.c_int32), ("reserved", C.c_uint32 * 4)]
+
+
+class UpdateStats(C.Structure):
+    _fields_ = [("ms", C.c_float), ("ms_device", C.c_float), ("root_min", C.c_float * 3), ("root_max", C.c_float * 3),
+                ("nodes", C.c_uint32), ("levels", C.c_uint32), ("launches", C.c_uint32), ("reserved", C.c_uint32)]
+
+    def as_dict(self):
+        return {"ms": self.ms, "ms_device": self.ms_device, "root_min": tuple(self.root_min),
+                "root_max": tuple(self.root_max), "nodes": self.nodes, "levels": self.levels,
+                "launches": self.launches}
+
+
 # exported entry points: name -> (restype, argtypes)
 SIGNATURES = {
     "nori_gpu_last_error": (C.c_char_p, []),
@@ -177,6 +193,10 @@ SIGNATURES = {
                                  C.POINTER(Stats)]),
     "nori_scene_surface": (C.c_int, [C.POINTER(SceneDesc), C.c_uint32, C.POINTER(C.c_float), C.c_void_p, C.c_void_p]),
     "nori_gpu_camera_rays": (C.c_int, [C.c_void_p, C.POINTER(RenderDesc), C.c_void_p]),
+    "nori_gpu_update_vertices": (C.c_int, [C.c_void_p, C.POINTER(UpdateDesc), C.POINTER(UpdateStats)]),
+    "nori_gpu_bvh_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint32)]),
+    "nori_scene_bvh_refit": (C.c_int, [C.POINTER(SceneDesc), C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                       C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "nori_gpu_cancel": (C.c_int, [C.c_void_p]),
     "nori_gpu_progress": (C.c_float, [C.c_void_p]),
     "nori_gpu_destroy": (None, [C.c_void_p]),
@@ -194,7 +214,8 @@ SIGNATURES = {
 }
 
 # entry points added without an ABI bump (no existing signature or struct changed)
-ADDED_IN_7 = {"nori_gpu_query", "nori_scene_surface", "nori_gpu_camera_rays"}
+ADDED_IN_7 = {"nori_gpu_query", "nori_scene_surface", "nori_gpu_camera_rays", "nori_gpu_update_vertices",
+              "nori_gpu_bvh_read", "nori_scene_bvh_refit"}
 
 COMM_ID_BYTES = 128
 SHARD_PASSES, SHARD_BLOCKS = 0, 1
