@@ -1,4 +1,9 @@
-// kernels.h -- launch wrappers for the gfx950 kernels (kernels.hip).
+// kernels.h -- launch wrappers for the gfx950 kernels.  Each launch_* is
+// defined beside its kernel: launch_shade in kernels_shade.hip; launch_mark,
+// launch_tail_prefix and launch_finish in kernels_finish.hip; launch_features
+// in kernels_features.hip; launch_surface and launch_camera_rays in
+// kernels_query.hip; the denoisers, the block error and the refit in
+// denoise.hip, block_error.hip and refit.hip; all others in kernels.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -8,7 +8,7 @@
 // values (the device decodes the packed angles and RGBE through the same
 // tables, so only 16 bytes per candidate photon are read).  The reference's kd-tree (kdtree.h) answers "every photon with
 // |x - p|^2 < r^2"; here a hash grid of cell size r answers the same query
-// from the 27 cells around p (kernels.hip, OneBounce::Li_pmap).
+// from the 27 cells around p (onebounce.h, OneBounce::Li_pmap).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -36,7 +36,7 @@ struct PhotonTables {  // PhotonData::initialize (photon.cpp:30-41)
     }
 };
 
-uint32_t cell_hash(const float *p, float ic) {  // == kernels.hip: (int)floorf(p * ic), photon_cell_hash
+uint32_t cell_hash(const float *p, float ic) {  // == onebounce.h Li_pmap: (int)floorf(p * ic), photon_cell_hash
     const int x = (int)std::floor(p[0] * ic), y = (int)std::floor(p[1] * ic), z = (int)std::floor(p[2] * ic);
     return ((uint32_t)x * 73856093u) ^ ((uint32_t)y * 19349663u) ^ ((uint32_t)z * 83492791u);
 }

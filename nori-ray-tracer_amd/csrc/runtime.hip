@@ -96,7 +96,7 @@ static float filter_eval(const nori_camera_desc &c, float x) {
     return 0.0f;
 }
 static int film_border(const nori_camera_desc &c) { return (int)std::ceil(c.filter_radius - 0.5f); }
-// k_splat's weights from a jitter class (kernels.hip jit_class) need every
+// k_splat's weights from a jitter class (device_math.h jit_class) need every
 // step of ImageBlock::put's index arithmetic exact: a power-of-two radius and
 // lookup factor (radius * lookup = NORI_FILTER_RESOLUTION), lookup <= 64 so
 // that a class fits 8 bits.  The reference's default radii (gaussian and
@@ -422,13 +422,13 @@ void mark_solitary_spheres(const nori_scene_desc &d, const float rmin[3], const 
     }
 }
 
-// The scan list of scan-mode scenes (kernels.hip scan_core).  Triangles that
+// The scan list of scan-mode scenes (scan.h scan_core).  Triangles that
 // lie in an axis plane -- both edges with an exactly zero component on the
 // same axis a, so every vertex has x_a = c -- come first, paired by plane:
 // the kernels skip such a pair for a whole wave when no ray of the wave can
 // hit it, a test that is exact only under the conditions checked here (no
 // cancellation in the one remaining product difference of det and of t's
-// numerator, kernels.hip plane_may_hit).  Pairs are ordered by axis (the
+// numerator, scan.h plane_may_hit).  Pairs are ordered by axis (the
 // kernels loop over each axis separately); a plane holding an odd number of
 // triangles pads its last pair with a record no ray hits.  The remaining
 // triangles follow, padded to kScanGroup, then the spheres.  Every record
@@ -444,7 +444,7 @@ struct ScanList {
     uint32_t real = 0;          // ... of which the last real one ends here (the padding after it never hits)
 };
 
-// The in-plane filter of the binned extension kernel (kernels.hip
+// The in-plane filter of the binned extension kernel (scan.h
 // pair_candidate): a ray can be accepted by the Moller-Trumbore test of a
 // triangle of pair g only if its crossing with the pair's plane x_A = c lies
 // within the pair's in-plane bounding rectangle widened by a margin M that
@@ -1036,7 +1036,7 @@ void upload_scene(nori_gpu_ctx &c, const nori_scene_desc &d) {
     if (S.border > 4) throw NoriException(NORI_ERR_UNSUPPORTED, "filter radius above 4.5 pixels");
     S.jit_lk = jit_code_lookup(S.filter_radius, S.lookup);
     S.integrator = d.integrator;
-    {  // deviation D10 (kernels.hip skip_nee); NORI_DISCRETE_NEE=1 keeps the full NEE everywhere
+    {  // deviation D10 (shading.h skip_nee); NORI_DISCRETE_NEE=1 keeps the full NEE everywhere
         bool env = false;
         for (uint32_t i = 0; i < d.num_emitters; ++i) env = env || d.emitters[i].type == NORI_EMITTER_ENVMAP;
         const char *e = std::getenv("NORI_DISCRETE_NEE");
@@ -2581,7 +2581,7 @@ int nori_scene_bvh_refit(const nori_scene_desc *d, const float *positions, float
 }
 
 // The hit record's statement (nori_gpu.h): fp32, the operation order of
-// k_surface (kernels.hip surface_record), which it is tested against bit for bit.
+// k_surface (kernels_query.hip surface_record), which it is tested against bit for bit.
 int nori_scene_surface(const nori_scene_desc *d, uint32_t n, const float *rays, const nori_gpu_hit *hits,
                        nori_gpu_surface *out) {
     return guarded([&] {

@@ -54,7 +54,7 @@ static void run(const std::vector<uint32_t> &cnt, uint32_t per, uint32_t B, uint
 }
 
 int main() {
-    // the launch shapes of kernels.hip: BVH walks (kTraceBlock = 128 threads,
+    // the launch shapes of the trace kernels (kernels.hip): BVH walks (kTraceBlock = 128 threads,
     // one ray), k_extend_scan (256 threads, 2 rays), k_shadow_scan (256, 1)
     struct Shape {
         uint32_t B, K;

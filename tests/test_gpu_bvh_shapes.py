@@ -1,4 +1,4 @@
-"""The BVH walk (kernels.hip traverse<STACK, ANY>) off its easy operating point, against the CPU
+"""The BVH walk (traverse.h traverse<STACK, ANY>) off its easy operating point, against the CPU
 oracle: deep chains at every traversal stack that may hold them, the three stacks against each
 other, reference leaves larger than the device's 64-primitive leaves, the scan/BVH switch, every
 kernel that walks the tree at stack 32, and the refusal of a tree no stack can hold.

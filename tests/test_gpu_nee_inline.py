@@ -1,5 +1,5 @@
 """GPU: next-event shadow rays traced inside the shade kernel (S.nee_inline,
-kernels.hip k_shade: the work-group's shadow rays compacted into LDS slots,
+kernels_shade.hip k_shade: the work-group's shadow rays compacted into LDS slots,
 any hit through the wave-uniform scan, then one read-modify-write of each
 sample record -- emission first, then the unoccluded NEE term, the order of
 the separate k_shadow_scan launch) against the shadow queue

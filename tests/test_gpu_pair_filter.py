@@ -1,4 +1,4 @@
-"""GPU: the scan's in-plane wall-pair filter (kernels.hip pair_candidate,
+"""GPU: the scan's in-plane wall-pair filter (scan.h pair_candidate,
 the CULL = 2 skip that k_extend_scan applies to waves of camera rays) drops no
 hit.  The trace API runs the scan with the filter (NORI_TRACE_CULL=2, read at
 context creation) and without any skip (NORI_TRACE_CULL=0) on the adversarial

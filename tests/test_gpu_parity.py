@@ -260,7 +260,7 @@ def test_render_modes_agree(built, mode):
 
 
 def test_plane_cull_same_hits(built):
-    """The scan's exact axis-plane culls (kernels.hip plane_may_hit: a wave
+    """The scan's exact axis-plane culls (scan.h plane_may_hit: a wave
     skips a wall pair that no ray of it can hit) against the scan without
     them (NORI_PLANE_CULL=0, read at context creation): the same hit on every
     ray -- t bit for bit -- and the same image up to the film sums' order.

@@ -1,4 +1,4 @@
-"""The binned extension kernel's in-plane filter (kernels.hip pair_candidate,
+"""The binned extension kernel's in-plane filter (scan.h pair_candidate,
 constants from runtime.hip plane_filters) is exact: whenever it says a ray
 cannot hit an axis-plane pair, the reference's Moller-Trumbore test
 (mesh.cpp:83-120) rejects that ray for both triangles of the pair.  Checked in
@@ -23,7 +23,7 @@ def fma(a, b, c):
 
 
 def pair_candidate(A, f, o, d, mint, maxt):
-    """kernels.hip pair_candidate<A> with f = the pair's 8 filter floats."""
+    """scan.h pair_candidate<A> with f = the pair's 8 filter floats."""
     B, C = (A + 1) % 3, (A + 2) % 3
     with np.errstate(all="ignore"):
         rcp = (f32(1) / d[:, A]).astype(f32)

@@ -1,4 +1,4 @@
-"""The scan's axis-plane cull (kernels.hip plane_may_hit) is exact: whenever
+"""The scan's axis-plane cull (scan.h plane_may_hit) is exact: whenever
 it says a ray cannot hit a triangle lying in an axis plane, the reference's
 Moller-Trumbore test (mesh.cpp:83-120) rejects that ray.  Checked here in
 float32 arithmetic with the device's evaluation order (device_math.h cross /
@@ -38,7 +38,7 @@ def moller_trumbore(p0, e1, e2, o, d, mint, maxt):
 
 
 def may_hit(o, d, c, mint, maxt):
-    """kernels.hip plane_may_hit (no bound on a side where mint <= 0 / maxt <= 0)."""
+    """scan.h plane_may_hit (no bound on a side where mint <= 0 / maxt <= 0)."""
     with np.errstate(all="ignore"):
         T = o - c
         ad = np.abs(d)
@@ -119,7 +119,7 @@ def test_cull_with_zero_mint_keeps_plane_hits(built):
 
 
 def moller_trumbore_plane(p0, e1, e2, o, d, mint, maxt, A):
-    """kernels.hip tri_hit_plane<A>: the products with the zero components left out."""
+    """scan.h tri_hit_plane<A>: the products with the zero components left out."""
     with np.errstate(all="ignore"):
         tv = (o[0] - p0[0], o[1] - p0[1], o[2] - p0[2])
         if A == 0:

@@ -1,4 +1,4 @@
-"""The axis-plane proofs (kernels.hip plane_may_hit, pair_candidate) hold for
+"""The axis-plane proofs (scan.h plane_may_hit, pair_candidate) hold for
 kappa = (|P| + |Q|) / |P - Q| <= 32 of a triangle's normal products, which
 runtime.hip axis_plane checks.  The Cornell box's rectangles have kappa = 1;
 here skewed sliver triangles in y = const planes span kappa 1.5 .. 64: the

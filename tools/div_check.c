@@ -1,4 +1,4 @@
-/* Checks the division used by the scan's sphere test (kernels.hip div_rn):
+/* Checks the division used by the scan's sphere test (scan.h sphere_hit_fast):
  * q = x / y correctly rounded from r = RN(1 / y), q0 = RN(x r),
  * e = fma(-y, q0, x) (exact), q = RN(q0 + e r) -- Markstein's theorem -- for
  * 2^-100 <= |x| <= 2^100 and y in the reciprocal's verified range.  Random
