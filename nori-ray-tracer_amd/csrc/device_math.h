@@ -48,8 +48,9 @@ NHD V3 cross(V3 a, V3 b) {
 // sqrtf, correctly rounded, in a shorter dependent chain: v_sqrt_f32 (about
 // 1 ulp) then one Tuckerman test each way (29 instead of 52 ns of lone-lane
 // latency, tools/latency_probe.hip).  Bit-identical to the IEEE sqrtf for
-// every float in [2^-96, 2^96) (tools/sqrt_check.hip, exhaustive); the IEEE
-// sequence runs outside that range.  FAST = true selects it in the templates
+// every float in [2^-96, 2^96) (tools/sqrt_check.hip, exhaustive; the suite
+// re-checks 4096 mantissas of every exponent and the switch points in
+// tests/test_gpu_device_units.py); the IEEE sequence runs outside that range.  FAST = true selects it in the templates
 // below (the tail finisher's glass-sphere chain, kernels.hip glass_bounce).
 NHD float sqrt_rn(float x) {
 #ifdef __HIP_DEVICE_COMPILE__
@@ -83,7 +84,8 @@ ND V3 ld3(const float4 &f) { return V3{f.x, f.y, f.z}; }
 // 1.0f / x, correctly rounded: v_rcp_f32 (~1 ulp) and one FMA Newton step
 // (3 VALU instead of the 9 of the IEEE division sequence).  Verified
 // bit-identical to the IEEE quotient for every float with |x| in
-// [2^-125, 2^125] by tools/rcp_check.hip; outside that range (and for
+// [2^-125, 2^125] by tools/rcp_check.hip (exhaustive; sampled again by
+// tests/test_gpu_device_units.py); outside that range (and for
 // inf/NaN) the IEEE division runs.  Below 2^-125 the triangle test never
 // uses the value (|det| < 1e-8 is rejected, mesh.cpp:96).
 ND float rcp_rn(float x) {

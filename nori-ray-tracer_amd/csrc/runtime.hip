@@ -21,6 +21,7 @@
 #include <string>
 #include <vector>
 
+#include "bsdf_desc.h"
 #include "comm.h"
 #include "host_scene.h"
 #include "kernels.h"
@@ -768,29 +769,7 @@ void upload_scene(nori_gpu_ctx &c, const nori_scene_desc &d) {
     for (uint32_t i = 0; i < d.num_bsdfs; ++i) {
         const nori_bsdf_desc &b = d.bsdfs[i];
         DevBsdf &o = bsdfs[i];
-        std::memset(&o, 0, sizeof(o));
-        o.type = b.type;
-        for (int k = 0; k < 3; ++k) o.albedo[k] = b.albedo[k], o.kd[k] = b.kd[k], o.base[k] = b.base_color[k];
-        o.int_ior = b.int_ior;
-        o.ext_ior = b.ext_ior;
-        o.eta_ei = b.ext_ior / b.int_ior;  // the divisions of common.cpp:296 / dielectric.cpp:57-60, done once
-        o.eta_ie = b.int_ior / b.ext_ior;
-        o.inv_eta_ei = 1 / o.eta_ei;
-        o.alpha = b.alpha;
-        float mk = b.kd[0] < b.kd[1] ? b.kd[1] : b.kd[0];
-        mk = mk < b.kd[2] ? b.kd[2] : mk;
-        o.ks = 1 - mk;  // microfacet.cpp:45
-        o.metallic = b.metallic;
-        o.specular = b.specular;
-        o.roughness = b.roughness;
-        o.sheen = b.sheen;
-        o.sheen_tint = b.sheen_tint;
-        o.spec_tint = b.specular_tint;
-        double r2 = (double)b.roughness * (double)b.roughness;  // disney.cpp:59
-        o.d_alpha = (float)(r2 > 1e-3 ? r2 : 1e-3);
-        o.tex = b.albedo_texture;
-        for (int k = 0; k < 3; ++k) o.tex_v2[k] = b.tex_value2[k];
-        for (int k = 0; k < 2; ++k) o.tex_delta[k] = b.tex_delta[k], o.tex_scale[k] = b.tex_scale[k];
+        dev_bsdf_from_desc(b, o);  // desc values and derived constants (bsdf_desc.h)
         if (b.albedo_texture == NORI_TEXTURE_IMAGE) {
             o.img = image_ptr(b.albedo_image);
             if (!o.img) throw NoriException(NORI_ERR_INVALID, "ImageTexture albedo without an image");

@@ -2164,6 +2164,24 @@ int oracle_bsdf_ttest(const nori_bsdf_desc *bd, float angle_deg, uint32_t n, dou
     return NORI_OK;
 }
 
+/* uv: the records' texture coordinates (n x 2), or NULL for (0, 0);
+ * sample: out = n x 8 (wo.xyz, weight rgb, weight luminance, measure) */
+int oracle_bsdf_sample_uv(const nori_bsdf_desc *bd, const float *wi, const float *u2, const float *uv, uint32_t n,
+                          float *out) {
+    Bsdf b; bsdf_init(&b, bd, NULL);
+    for (uint32_t i = 0; i < n; ++i) {
+        BRec br; memset(&br, 0, sizeof(br));
+        br.wi = v3(wi[3 * i], wi[3 * i + 1], wi[3 * i + 2]);
+        if (uv) { br.uv.x = uv[2 * i]; br.uv.y = uv[2 * i + 1]; }
+        V2 smp = {u2[2 * i], u2[2 * i + 1]};
+        V3 w = bsdf_sample(&b, &br, smp);
+        float *o = out + 8 * (size_t)i;
+        o[0] = br.wo.x; o[1] = br.wo.y; o[2] = br.wo.z; o[3] = w.x; o[4] = w.y; o[5] = w.z;
+        o[6] = lum(w); o[7] = (float)br.measure;
+    }
+    return NORI_OK;
+}
+
 int oracle_bsdf_sample(const nori_bsdf_desc *bd, const float *wi, const float *u2, uint32_t n, float *out) {
     Bsdf b; bsdf_init(&b, bd, NULL);
     for (uint32_t i = 0; i < n; ++i) {
@@ -2177,15 +2195,21 @@ int oracle_bsdf_sample(const nori_bsdf_desc *bd, const float *wi, const float *u
     return NORI_OK;
 }
 
-int oracle_bsdf_eval_pdf(const nori_bsdf_desc *bd, const float *wi, const float *wo, uint32_t n, float *out) {
+int oracle_bsdf_eval_pdf_uv(const nori_bsdf_desc *bd, const float *wi, const float *wo, const float *uv, uint32_t n,
+                            float *out) {
     Bsdf b; bsdf_init(&b, bd, NULL);
     for (uint32_t i = 0; i < n; ++i) {
         BRec br; memset(&br, 0, sizeof(br));
         br.wi = v3(wi[3 * i], wi[3 * i + 1], wi[3 * i + 2]); br.wo = v3(wo[3 * i], wo[3 * i + 1], wo[3 * i + 2]);
+        if (uv) { br.uv.x = uv[2 * i]; br.uv.y = uv[2 * i + 1]; }
         br.measure = M_SOLID_ANGLE; br.eta = 1.0f;
         V3 f = bsdf_eval(&b, &br);
         float *o = out + 4 * (size_t)i;
         o[0] = f.x; o[1] = f.y; o[2] = f.z; o[3] = bsdf_pdf(&b, &br);
     }
     return NORI_OK;
+}
+
+int oracle_bsdf_eval_pdf(const nori_bsdf_desc *bd, const float *wi, const float *wo, uint32_t n, float *out) {
+    return oracle_bsdf_eval_pdf_uv(bd, wi, wo, NULL, n, out);
 }

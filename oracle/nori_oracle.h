@@ -82,6 +82,13 @@ int oracle_bsdf_sample(const nori_bsdf_desc *bsdf, const float *wi, const float 
                        uint32_t n, float *out);
 int oracle_bsdf_eval_pdf(const nori_bsdf_desc *bsdf, const float *wi, const float *wo,
                          uint32_t n, float *out /* n x 4: f.rgb, pdf */);
+/* The same with the records' texture coordinates uv (n x 2, NULL: (0, 0)), so
+ * a checkerboard albedo is reached; sample: out = n x 8 (wo.xyz, weight rgb,
+ * weight luminance, measure). */
+int oracle_bsdf_sample_uv(const nori_bsdf_desc *bsdf, const float *wi, const float *u2, const float *uv,
+                          uint32_t n, float *out);
+int oracle_bsdf_eval_pdf_uv(const nori_bsdf_desc *bsdf, const float *wi, const float *wo, const float *uv,
+                            uint32_t n, float *out);
 
 #ifdef __cplusplus
 }

@@ -56,6 +56,8 @@ def lib():
             "oracle_bsdf_ttest": (C.c_int, [vp, f32, u32, pd, pd]),
             "oracle_bsdf_sample": (C.c_int, [vp, pf, pf, u32, pf]),
             "oracle_bsdf_eval_pdf": (C.c_int, [vp, pf, pf, u32, pf]),
+            "oracle_bsdf_sample_uv": (C.c_int, [vp, pf, pf, pf, u32, pf]),
+            "oracle_bsdf_eval_pdf_uv": (C.c_int, [vp, pf, pf, pf, u32, pf]),
             "oracle_photon_map": (C.c_int, [vp, C.POINTER(u64), C.POINTER(u32), C.POINTER(pf)]),
         }
         for name, (res, args) in sig.items():
@@ -191,4 +193,25 @@ def bsdf_eval_pdf(bsdf_desc, wi, wo):
     wo = np.ascontiguousarray(wo, np.float32)
     out = np.zeros((wi.shape[0], 4), np.float32)
     lib().oracle_bsdf_eval_pdf(C.byref(bsdf_desc), _fp(wi), _fp(wo), wi.shape[0], _fp(out))
+    return out
+
+
+def bsdf_sample_uv(bsdf_desc, wi, u2, uv=None):
+    """(n, 8): wo, weight rgb, weight luminance, measure; uv (n, 2) or None for (0, 0)."""
+    wi = np.ascontiguousarray(wi, np.float32)
+    u2 = np.ascontiguousarray(u2, np.float32)
+    uv = np.ascontiguousarray(uv, np.float32) if uv is not None else None
+    out = np.zeros((wi.shape[0], 8), np.float32)
+    lib().oracle_bsdf_sample_uv(C.byref(bsdf_desc), _fp(wi), _fp(u2), _fp(uv) if uv is not None else None,
+                                wi.shape[0], _fp(out))
+    return out
+
+
+def bsdf_eval_pdf_uv(bsdf_desc, wi, wo, uv=None):
+    wi = np.ascontiguousarray(wi, np.float32)
+    wo = np.ascontiguousarray(wo, np.float32)
+    uv = np.ascontiguousarray(uv, np.float32) if uv is not None else None
+    out = np.zeros((wi.shape[0], 4), np.float32)
+    lib().oracle_bsdf_eval_pdf_uv(C.byref(bsdf_desc), _fp(wi), _fp(wo), _fp(uv) if uv is not None else None,
+                                  wi.shape[0], _fp(out))
     return out
