@@ -7,6 +7,8 @@ frame is written:
 
   1. torch                                        the rest positions displaced by an expression of the time
   2. GpuRenderer.update_vertices(tensor)          pos / triangle records rewritten, boxes refitted (no rebuild)
+     GpuRenderer.rebuild_bvh()                    with --rebuild-every N, every N-th frame: a new tree for the
+                                                  positions as they are now, built on the GPU
   3. GpuRenderer.camera_rays(out=tensor)          the renderer's own primary rays
   4. GpuRenderer.query(rays, surf_out=...)        closest hits on the new geometry: a normals image
 
@@ -47,8 +49,10 @@ def normals_image(renderer, rays, surf):
     return img.reshape(scene.height, scene.width, 3)
 
 
-def deform_frames(renderer, frames=8, amplitude=0.05):
-    """`frames` normals images of the scene under displaced(): a list of (H, W, 3) cuda tensors."""
+def deform_frames(renderer, frames=8, amplitude=0.05, rebuild_every=0):
+    """`frames` normals images of the scene under displaced(): a list of (H, W, 3) cuda tensors.
+    rebuild_every = N > 0: the BVH is rebuilt on the device after the update of every N-th frame
+    (a refit keeps the topology chosen for the positions as loaded); 0: refits only."""
     scene = renderer.scene
     dev = torch.device("cuda", renderer.device)
     rest = torch.from_numpy(scene.positions()).to(dev)  # the one upload: the geometry as loaded
@@ -58,6 +62,8 @@ def deform_frames(renderer, frames=8, amplitude=0.05):
     out = []
     for f in range(frames):
         renderer.update_vertices(displaced(rest, f / max(frames, 1), amplitude))
+        if rebuild_every > 0 and (f + 1) % rebuild_every == 0:
+            renderer.rebuild_bvh()
         torch.cuda.synchronize(dev)
         out.append(normals_image(renderer, rays, surf).clone())
     return out
@@ -71,11 +77,13 @@ def main():
     ap.add_argument("--height", type=int, default=0)
     ap.add_argument("--frames", type=int, default=8)
     ap.add_argument("--amplitude", type=float, default=0.05)
+    ap.add_argument("--rebuild-every", type=int, default=0, metavar="N",
+                    help="rebuild the BVH on the device every N-th frame (default 0: refit only)")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args()
     scene = nori_amd.load_scene(a.scene, a.width, a.height, 1)
     with nori_amd.GpuRenderer(scene, a.device) as r:
-        imgs = deform_frames(r, a.frames, a.amplitude)
+        imgs = deform_frames(r, a.frames, a.amplitude, a.rebuild_every)
     for i, img in enumerate(imgs):
         nori_amd.write_png(f"{a.output}_{i:03d}.png", img.cpu().numpy())  # the first host copy of a frame
     print(f"{a.output}_000.png .. {len(imgs) - 1:03d}.png: {scene.width}x{scene.height}")

@@ -46,6 +46,10 @@
  *                         (dynamic geometry: new vertex positions and a BVH
  *                          refit on the device; no reference counterpart, the
  *                          reference builds its BVH once in Scene::activate)
+ *   nori_gpu_rebuild_bvh, nori_scene_bvh_rebuild
+ *                         (dynamic geometry: a linear BVH built on the device
+ *                          for the positions as they are now; no reference
+ *                          counterpart)
  *   nori_gpu_comm_*, nori_gpu_render_sharded
  *                         <- the same pass loop spread over the GPUs of a node,
  *                            one process per GPU; the cross-GPU film merge is
@@ -691,6 +695,104 @@ int nori_scene_bvh_refit(const nori_scene_desc *scene, const float *positions, f
  *   pass of its own before anything is modified, device buffers included).
  * stats may be NULL. */
 int nori_gpu_update_vertices(nori_gpu_ctx *ctx, const nori_gpu_update_desc *desc, nori_gpu_update_stats *stats);
+/* ---- dynamic geometry: the BVH rebuilt for the positions as they are now ----
+ * (deviation D15).  A refit keeps the topology the SAH builder chose
+ * for the positions as loaded; after a large displacement that tree traces
+ * slowly.  The rebuild is a linear BVH -- Morton keys, a sort, a radix tree
+ * emitted 4-wide -- stated here once and reproduced by the kernels of
+ * nori_gpu_rebuild_bvh byte for byte.  The tree is a function of the scene,
+ * the positions and leaf_max only; every step is integer arithmetic or fp32
+ * with a stated operation order (contraction is off in this build), so any
+ * correct implementation gives the same bytes.
+ *
+ * Primitive boxes.  Primitives are numbered by their global id, in shape
+ *   order; a sphere is one primitive.  A triangle's box is the box_min /
+ *   box_max (min / max with ordered zeros, -0 < +0, as in the refit) over its
+ *   three vertex positions; a sphere's is centre -/+ radius in fp32.  The scene
+ *   box Lo, Hi is the box_min / box_max over all primitive boxes.
+ * Keys.  Per axis, in fp32: c = 0.5f * lo + 0.5f * hi of the primitive's box,
+ *   ext = Hi - Lo, scale = ext > 0 ? 1024.0f / ext : 0.0f (one correctly
+ *   rounded division), x = (c - Lo) * scale,
+ *   q = !(x >= 0) ? 0 : x >= 1023 ? 1023 : (uint32_t)x   (a NaN from inf * 0
+ *   gives 0).  The 30-bit Morton code has bit 3k+2 = bit k of qx, bit 3k+1 =
+ *   bit k of qy, bit 3k = bit k of qz.  The sort key is the 64-bit
+ *   code << 32 | id: keys are unique, so every correct sort gives the same
+ *   order.  Leaf order is ascending key.
+ * Records.  The ones nori_gpu_create writes for the same positions, in the new
+ *   leaf order: triangle (p0 | id), (p1 - p0 | 0), (p2 - p0 | 0); sphere
+ *   (centre | id), (r, 0, 0, 1), 0.
+ * Topology.  Let K[i] = code_i << 32 | i with i the position in leaf order.  A
+ *   range [a, b] of more than leaf_max records is split after g, the largest
+ *   index in [a, b) whose K shares more leading bits with K[a] than K[b] does
+ *   (Karras 2012); equal codes therefore split on the bits of the position, so
+ *   a cluster of ties gets a balanced subtree.  A range of at most leaf_max
+ *   records is a leaf, its ref leaf bit | (count - 1) << 25 | first.  The
+ *   4-wide node of a range R takes R's two halves and replaces every half that
+ *   is not a leaf by its own two halves, in place and in order: 2 to 4 used
+ *   slots, filled from slot 0; unused slots get the ref `leaf bit` and a NaN
+ *   box.  The root is node 0; when n <= leaf_max it has one leaf slot.  Nodes
+ *   are numbered breadth-first: the nodes of depth d + 1 follow those of depth
+ *   d, ordered by (parent number, slot).  `depth` is the number of levels.
+ * Boxes.  Exactly what nori_scene_bvh_refit states on this topology: leaf
+ *   slots from the vertex positions with ordered zeros, inner slots from the
+ *   child's used slots; root_box as there.
+ *
+ * positions: num_vertices x 3 floats, NULL = the scene's own.  leaf_max:
+ * 1 .. 64, 0 = the default, 4.  refit_positions (optional): the finished tree
+ * is then refitted to them exactly as nori_scene_bvh_refit states (what a
+ * nori_gpu_update_vertices after a nori_gpu_rebuild_bvh gives).  info, nodes
+ * (32 floats per node), prims (12 floats per record) and root_box may each be
+ * NULL: call with info alone for the sizes.  NORI_ERR_INVALID: a null scene, a
+ * non-finite position, leaf_max > 64. */
+typedef struct nori_bvh_rebuild_info {
+    uint32_t device_nodes, depth, num_prims, leaf_max;  /* leaf_max: the value used */
+    uint32_t reserved[4];
+} nori_bvh_rebuild_info;
+int nori_scene_bvh_rebuild(const nori_scene_desc *scene, const float *positions, uint32_t leaf_max,
+                           const float *refit_positions, nori_bvh_rebuild_info *info, float *nodes, float *prims,
+                           float root_box[6]);
+
+typedef struct nori_gpu_rebuild_desc {
+    uint32_t leaf_max;       /* 1 .. 64; 0 = the default, 4 */
+    uint32_t reserved[7];    /* must be 0 */
+} nori_gpu_rebuild_desc;
+typedef struct nori_gpu_rebuild_stats {
+    float ms;                /* wall time of the call (host timer)                    */
+    float ms_device;         /* HIP-event time from the first launch to the last      */
+    uint32_t nodes, depth;   /* the new tree: 4-wide nodes, levels                    */
+    uint32_t stack;          /* the traversal stack now in use (8, 16 or 32)          */
+    uint32_t levels;         /* levels of the new refit schedule                      */
+    uint32_t launches;       /* kernel launches of this library (the sort's and the scan's own not counted) */
+    uint32_t reserved;
+} nori_gpu_rebuild_stats;
+/* Rebuilds the context's BVH on the vertex positions the context holds now
+ * (as created, or as set by the last nori_gpu_update_vertices), all on the
+ * device: the result is byte for byte nori_scene_bvh_rebuild's tree for those
+ * positions (nori_gpu_bvh_read shows it).  The scene box is reduced with
+ * integer atomics on an order-preserving key, the keys are sorted with
+ * rocprim's radix sort, the tree is emitted one breadth-first level per
+ * launch set (the host reads one pair of counts back per level and checks it
+ * against its bound before it sizes the next launches) and the boxes are
+ * fitted by the refit's own kernel.  Everything is built in scratch buffers
+ * of the context; on success the nodes, the records, the refit schedule, the
+ * depth, node count, traversal stack (nori_gpu_create's rule for the new
+ * depth; a stack forced by NORI_BVH_STACK at creation stays forced) and the
+ * scene box are replaced together, and later nori_gpu_update_vertices calls
+ * refit the rebuilt tree.  The light CDFs, the spheres' `solitary` flags, the
+ * vertex buffers and everything else stay.  Hit distances and barycentrics
+ * are those of any other tree over the same records, bit for bit.
+ * Blocking; runs on the context's stream: concurrent use with a render or
+ * query of the same context is not supported.
+ * Refused with nothing changed (the context traces and renders exactly as
+ * before):
+ * NORI_ERR_UNSUPPORTED -- a scan-mode context (create it with
+ *   NORI_TRAVERSAL=bvh), a photonmapper context (the same surface as
+ *   nori_gpu_update_vertices), a tree too deep for the traversal stack
+ *   (binary depth is at most 30 + ceil(log2 n), the 4-wide depth about half
+ *   of it: ordinary scenes are far inside the limit);
+ * NORI_ERR_INVALID -- a null ctx or desc, leaf_max > 64, reserved != 0.
+ * stats may be NULL. */
+int nori_gpu_rebuild_bvh(nori_gpu_ctx *ctx, const nori_gpu_rebuild_desc *desc, nori_gpu_rebuild_stats *stats);
 /* Introspection for tests, like nori_scene_scan_list: the context's BVH nodes
  * (32 floats per node) and primitive records (12 floats per record, leaf
  * order; a scan-mode context holds its scan list there) as they are on the

@@ -109,6 +109,12 @@ void refit_host(DeviceBvh &bvh, const RefitPlan &plan, const std::vector<uint32_
                 float root_box[6]);
 void refit_root_box(const float *root_node, float box[6]);
 
+// ---- BVH rebuild (bvh_rebuild.cpp; stated at nori_scene_bvh_rebuild in nori_gpu.h)
+// The linear BVH of the scene's primitives at `positions` (null: the scene's
+// own) with leaves of at most leaf_max records (0: the default): nodes
+// breadth-first, records in ascending key order, boxes fitted by refit_host.
+void rebuild_host(const nori_scene_desc &d, const float *positions, uint32_t leaf_max, DeviceBvh &out);
+
 // Photon map (photon_map.cpp): raw = n photons x 12 floats (position, 0,
 // direction towards the light, 0, power, 0) in emission order -> photons as
 // (x, y, z, theta | phi << 8) and RGBE words (the reference's PhotonData),

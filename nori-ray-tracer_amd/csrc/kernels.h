@@ -173,5 +173,33 @@ hipError_t launch_refit_records(float4 *prims, const uint32_t *vidx, const float
 // (node, slot) entries of `slots`; the levels below have completed on `st`.
 hipError_t launch_refit_level(float4 *nodes, const float4 *prims, const uint32_t *vidx, const float4 *pos,
                               const uint32_t *slots, uint32_t n, hipStream_t st);
+// The BVH rebuild (rebuild.hip; stated at nori_scene_bvh_rebuild in nori_gpu.h).
+// All pointers are device memory; n = S's primitives (>= 1), read through
+// S.tri_vidx, S.pos, S.prim_shape and S.shapes.
+// box[0..2] / box[3..5] = min / max over the primitive boxes as order keys (rebuild.h).
+hipError_t launch_rebuild_scene_box(const DevScene &S, uint32_t n, uint32_t *box, hipStream_t st);
+// keys[id] = Morton code << 32 | id on the grid (lo, scale) of the scene box.
+hipError_t launch_rebuild_keys(const DevScene &S, uint32_t n, const float lo[3], const float scale[3], uint64_t *keys,
+                               hipStream_t st);
+// rocprim's radix sort of the n keys / exclusive sum of n counts; temp == null: temp_bytes = the storage needed.
+hipError_t rebuild_sort_keys(void *temp, size_t &temp_bytes, const uint64_t *in, uint64_t *out, uint32_t n,
+                             hipStream_t st);
+hipError_t rebuild_scan_counts(void *temp, size_t &temp_bytes, const uint64_t *in, uint64_t *out, uint32_t n,
+                               hipStream_t st);
+// The n records in the order of the sorted keys.
+hipError_t launch_rebuild_records(const DevScene &S, const uint64_t *sorted, uint32_t n, float4 *prims, hipStream_t st);
+// A breadth-first level of m nodes with the record ranges `ranges`: split writes
+// each node's slots (ends) and count[0 .. m] (inner | leaf << 32, count[m] = 0);
+// after the exclusive scan of count, emit writes the nodes' compact refs at
+// refs[level_off ..], the next level's ranges, inner_slots[child - 1] and the
+// level's leaf slots from leaf_slots[leaf_base].  The caller has checked
+// level_off + m + the level's inner slots <= n and leaf_base + its leaf slots <= n.
+hipError_t launch_rebuild_split(const uint64_t *sorted, const uint2 *ranges, uint32_t m, uint32_t leaf_max, uint4 *ends,
+                                uint64_t *count, hipStream_t st);
+hipError_t launch_rebuild_emit(const uint2 *ranges, const uint4 *ends, const uint64_t *scan, uint32_t m,
+                               uint32_t level_off, uint32_t leaf_base, uint32_t leaf_max, uint4 *refs, uint2 *next,
+                               uint32_t *inner_slots, uint32_t *leaf_slots, hipStream_t st);
+// The N nodes (8 float4 each) from their compact refs: NaN boxes in the unused slots, zero boxes in the used ones.
+hipError_t launch_rebuild_nodes(const uint4 *refs, uint32_t N, float4 *nodes, hipStream_t st);
 
 }  // namespace nori

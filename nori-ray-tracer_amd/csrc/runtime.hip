@@ -25,6 +25,7 @@
 #include "comm.h"
 #include "host_scene.h"
 #include "kernels.h"
+#include "rebuild.h"
 
 namespace nori {
 
@@ -245,6 +246,13 @@ struct nori_gpu_ctx {
     DevBuf refit_slots, upd_pos, upd_nrm, upd_count;
     hipEvent_t upd_ev[2] = {};
     uint32_t num_vertices = 0;
+    // nori_gpu_rebuild_bvh: the stack NORI_BVH_STACK forced at creation (0: none), and the scratch
+    // the new tree is built in -- rb_nodes, rb_prims and rb_slots are swapped with nodes, prims
+    // and refit_slots on success, so a context that rebuilds holds two trees' worth of buffers
+    int stack_forced = 0;
+    DevBuf rb_box, rb_keys[2], rb_sort_tmp, rb_scan_tmp, rb_prims, rb_nodes, rb_refs, rb_ranges[2], rb_ends, rb_count,
+        rb_scan, rb_inner, rb_leaf, rb_slots;
+    hipEvent_t rb_ev[2] = {};
     std::vector<DevShape> hshapes;
     struct EmitterMesh {
         uint32_t shape, cdf_offset, vtx_first, vtx_count;  // the vertex range its triangles use
@@ -275,6 +283,8 @@ struct nori_gpu_ctx {
         for (auto e : q_ev)
             if (e) (void)hipEventDestroy(e);
         for (auto e : upd_ev)
+            if (e) (void)hipEventDestroy(e);
+        for (auto e : rb_ev)
             if (e) (void)hipEventDestroy(e);
         if (pinned) (void)hipHostFree(pinned);
         if (readback) (void)hipHostFree(readback);
@@ -315,6 +325,24 @@ template <class F> int guarded(F &&f) {
     } catch (const std::exception &e) {
         return fail(NORI_ERR_INVALID, e.what());
     }
+}
+
+// The traversal stack of a 4-wide tree of `depth` levels (nori_gpu_create and
+// nori_gpu_rebuild_bvh): at most 3 entries per level; the first `stack` live
+// in LDS, up to kTraceSpill more in private memory (an 8-wide tree, 256-B
+// nodes with a 19-comparator child order, was measured 15 % slower on C3 in
+// round 5: DESIGN_LOG.md).  LDS budget 16 words: measured best on the 22.7k
+// and 524k triangle scenes -- occupancy beats a deeper LDS part; 32 only when
+// the spill area could not cover the rest.  forced: NORI_BVH_STACK's 8, 16 or
+// 32 (tuning), or 0.  Throws for a tree too deep for the stack.
+int bvh_stack_for(uint32_t depth, int forced) {
+    const uint32_t need = 3 * depth + 1;
+    int stack = 32;
+    if (need <= (uint32_t)stack_lds_entries(8)) stack = 8;
+    else if (need <= (uint32_t)stack_lds_entries(16) + kTraceSpill) stack = 16;
+    if (forced) stack = forced;
+    if (need > (uint32_t)stack_lds_entries(stack) + kTraceSpill) throw NoriException(NORI_ERR_UNSUPPORTED, "BVH too deep for the traversal stack");
+    return stack;
 }
 
 // Scene box = BVH root box: every mesh vertex and every sphere's bounds.
@@ -833,22 +861,12 @@ void upload_scene(nori_gpu_ctx &c, const nori_scene_desc &d) {
     build_device_bvh(d, rmin, rmax, bvh);
     c.bvh_depth = bvh.depth;
     c.bvh_nodes = bvh.num_nodes;
-    // traversal stack: at most 3 entries per level of the 4-wide tree; the
-    // first `stack` live in LDS, up to kTraceSpill more in private memory
-    // (an 8-wide tree, 256-B nodes with a 19-comparator child order, was
-    // measured 15 % slower on C3 in round 5: DESIGN_LOG.md)
-    const uint32_t need = 3 * bvh.depth + 1;
-    // (LDS budget 16 words: measured best on the 22.7k and 524k triangle
-    // scenes -- occupancy beats a deeper LDS part; 32 only when the spill
-    // area could not cover the rest)
-    if (need <= (uint32_t)stack_lds_entries(8)) c.stack = 8;
-    else if (need <= (uint32_t)stack_lds_entries(16) + kTraceSpill) c.stack = 16;
-    else c.stack = 32;
-    if (const char *e = std::getenv("NORI_BVH_STACK")) {  // tuning: 8, 16 or 32
+    // traversal stack (bvh_stack_for); NORI_BVH_STACK = 8, 16 or 32 forces it (tuning)
+    if (const char *e = std::getenv("NORI_BVH_STACK")) {
         const int v = std::atoi(e);
-        if (v == 8 || v == 16 || v == 32) c.stack = v;
+        if (v == 8 || v == 16 || v == 32) c.stack_forced = v;
     }
-    if (need > (uint32_t)stack_lds_entries(c.stack) + kTraceSpill) throw NoriException(NORI_ERR_UNSUPPORTED, "BVH too deep for the traversal stack");
+    c.stack = bvh_stack_for(bvh.depth, c.stack_forced);
     if (scan) c.stack = 0;
     ScanList scan_list;
     if (scan) scan_list = build_scan_list(bvh, off);
@@ -1961,6 +1979,166 @@ int update_vertices(nori_gpu_ctx &c, const nori_gpu_update_desc &ud, nori_gpu_up
     return NORI_OK;
 }
 
+// nori_gpu_rebuild_bvh (stated in nori_gpu.h): a linear BVH for the positions
+// the context holds, built in the rb_* scratch buffers on the context's
+// stream and swapped in at the end; until then nothing the context renders
+// with is written, so every refusal and every failure leaves it as it was.
+int rebuild_bvh(nori_gpu_ctx &c, const nori_gpu_rebuild_desc &rd, nori_gpu_rebuild_stats *stats) {
+    const auto t0 = std::chrono::steady_clock::now();
+    if (c.stack == 0)
+        throw NoriException(NORI_ERR_UNSUPPORTED,
+                            "nori_gpu_rebuild_bvh: a scan-mode context; create the context with NORI_TRAVERSAL=bvh");
+    if (c.S.integrator == NORI_INTEGRATOR_PHOTONMAPPER)
+        throw NoriException(NORI_ERR_UNSUPPORTED,
+                            "nori_gpu_rebuild_bvh: a photonmapper context (its photon map was traced at creation)");
+    if (rd.leaf_max > kRebuildLeafMax) throw NoriException(NORI_ERR_INVALID, "nori_gpu_rebuild_bvh: leaf_max above 64");
+    for (uint32_t r : rd.reserved)
+        if (r != 0) throw NoriException(NORI_ERR_INVALID, "nori_gpu_rebuild_bvh: reserved must be 0");
+    const uint32_t L = rd.leaf_max ? rd.leaf_max : kRebuildLeafDefault;
+    const uint32_t n = c.S.num_prims;  // (a BVH context: one record per primitive, 1 <= n < 2^25)
+    if (n == 0 || n >= kRebuildMaxPrims) throw NoriException(NORI_ERR_UNSUPPORTED, "nori_gpu_rebuild_bvh: primitive count");
+    HIP_TRY(hipSetDevice(c.device));
+    for (auto &e : c.rb_ev)
+        if (!e) HIP_TRY(hipEventCreate(&e));
+    hipStream_t st = c.stream;
+    auto internal = [](const char *what) {
+        return NoriException(NORI_ERR_HIP, std::string("nori_gpu_rebuild_bvh: ") + what + " (nothing was changed)");
+    };
+    // ---- scratch, sized from n alone: a level has at most n / 2 nodes, the tree fewer than n
+    size_t sort_bytes = 0, scan_bytes = 0;
+    HIP_TRY(rebuild_sort_keys(nullptr, sort_bytes, nullptr, nullptr, n, st));
+    HIP_TRY(rebuild_scan_counts(nullptr, scan_bytes, nullptr, nullptr, n + 1, st));
+    c.rb_sort_tmp.ensure(sort_bytes);
+    c.rb_scan_tmp.ensure(scan_bytes);
+    c.rb_box.ensure(24);
+    for (auto &b : c.rb_keys) b.ensure(8 * (size_t)n);
+    for (auto &b : c.rb_ranges) b.ensure(8 * (size_t)n);
+    c.rb_ends.ensure(16 * (size_t)n);
+    c.rb_count.ensure(8 * ((size_t)n + 1));
+    c.rb_scan.ensure(8 * ((size_t)n + 1));
+    c.rb_refs.ensure(16 * (size_t)n);
+    c.rb_inner.ensure(4 * (size_t)n);
+    c.rb_leaf.ensure(4 * (size_t)n);
+    c.rb_prims.ensure(48 * (size_t)n);
+    uint32_t launches = 0;
+    // ---- the scene box, then the grid on the host (one division per axis)
+    HIP_TRY(hipEventRecord(c.rb_ev[0], st));
+    HIP_TRY(launch_rebuild_scene_box(c.S, n, c.rb_box.as<uint32_t>(), st));
+    uint32_t boxk[6];
+    HIP_TRY(hipMemcpyAsync(boxk, c.rb_box.p, sizeof(boxk), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    float lo[3], scale[3];
+    for (int k = 0; k < 3; ++k) {
+        lo[k] = rebuild_order_value(boxk[k]);
+        scale[k] = rebuild_scale(lo[k], rebuild_order_value(boxk[3 + k]));
+    }
+    // ---- keys, sort, records
+    uint64_t *keys = c.rb_keys[0].as<uint64_t>(), *sorted = c.rb_keys[1].as<uint64_t>();
+    HIP_TRY(launch_rebuild_keys(c.S, n, lo, scale, keys, st));
+    HIP_TRY(rebuild_sort_keys(c.rb_sort_tmp.p, sort_bytes, keys, sorted, n, st));
+    HIP_TRY(launch_rebuild_records(c.S, sorted, n, c.rb_prims.as<float4>(), st));
+    launches += 3;
+    // ---- topology, one breadth-first level per round
+    std::vector<uint32_t> node_begin{0};  // first node of every level, then the node count
+    uint32_t leaves = 0, depth = 0;
+    int stack = c.stack;
+    const uint32_t root_ref[4] = {kRefitLeafBit | ((n - 1) << 25), 0xffffffffu, 0xffffffffu, 0xffffffffu};
+    const uint32_t zero = 0, root_range[2] = {0, n - 1};
+    if (n <= L) {  // one node, one leaf slot
+        HIP_TRY(hipMemcpyAsync(c.rb_refs.p, root_ref, 16, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(c.rb_leaf.p, &zero, 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        node_begin.push_back(1);
+        leaves = depth = 1;
+        stack = bvh_stack_for(depth, c.stack_forced);
+    } else {
+        HIP_TRY(hipMemcpyAsync(c.rb_ranges[0].p, root_range, 8, hipMemcpyHostToDevice, st));
+        uint32_t m = 1, level_off = 0;
+        int cur = 0;
+        while (m) {  // (bvh_stack_for throws at the depth limit: at most 26 rounds)
+            stack = bvh_stack_for(++depth, c.stack_forced);
+            const uint2 *ranges = c.rb_ranges[cur].as<uint2>();
+            HIP_TRY(launch_rebuild_split(sorted, ranges, m, L, c.rb_ends.as<uint4>(), c.rb_count.as<uint64_t>(), st));
+            HIP_TRY(rebuild_scan_counts(c.rb_scan_tmp.p, scan_bytes, c.rb_count.as<uint64_t>(), c.rb_scan.as<uint64_t>(),
+                                        m + 1, st));
+            uint64_t total = 0;
+            HIP_TRY(hipMemcpyAsync(&total, c.rb_scan.as<uint64_t>() + m, 8, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            const uint64_t inner = total & 0xffffffffull, leaf = total >> 32;
+            // the counts size the next launches and index the lists: checked against their bounds first
+            if (inner + leaf < 2 * (uint64_t)m || inner + leaf > 4 * (uint64_t)m || (uint64_t)level_off + m + inner > n ||
+                (uint64_t)leaves + leaf > n)
+                throw internal("a level's slot counts are out of bounds");
+            HIP_TRY(launch_rebuild_emit(ranges, c.rb_ends.as<uint4>(), c.rb_scan.as<uint64_t>(), m, level_off, leaves, L,
+                                        c.rb_refs.as<uint4>(), c.rb_ranges[cur ^ 1].as<uint2>(),
+                                        c.rb_inner.as<uint32_t>(), c.rb_leaf.as<uint32_t>(), st));
+            launches += 2;
+            level_off += m;
+            node_begin.push_back(level_off);
+            leaves += (uint32_t)leaf;
+            m = (uint32_t)inner;
+            cur ^= 1;
+        }
+    }
+    const uint32_t N = node_begin.back();
+    // ---- the nodes, and the refit schedule: level 0 = every leaf slot, then the inner slots
+    // deepest level first (the inner slot of child node c is entry c - 1 of rb_inner)
+    c.rb_nodes.ensure(128 * (size_t)N);
+    HIP_TRY(launch_rebuild_nodes(c.rb_refs.as<uint4>(), N, c.rb_nodes.as<float4>(), st));
+    ++launches;
+    RefitPlan plan;  // (its host `slots` stay empty: the schedule is made on the device)
+    plan.level_begin = {0, leaves};
+    c.rb_slots.ensure(4 * ((size_t)leaves + N - 1));
+    uint32_t *slots = c.rb_slots.as<uint32_t>();
+    HIP_TRY(hipMemcpyAsync(slots, c.rb_leaf.p, 4 * (size_t)leaves, hipMemcpyDeviceToDevice, st));
+    for (uint32_t d = depth - 1; d-- > 0;) {  // node level d's inner slots = the nodes of level d + 1
+        const uint32_t b = node_begin[d + 1] - 1, cnt = node_begin[d + 2] - node_begin[d + 1];
+        HIP_TRY(hipMemcpyAsync(slots + plan.level_begin.back(), c.rb_inner.as<uint32_t>() + b, 4 * (size_t)cnt,
+                               hipMemcpyDeviceToDevice, st));
+        plan.level_begin.push_back(plan.level_begin.back() + cnt);
+    }
+    // ---- the boxes: the refit's kernel over the new schedule
+    for (uint32_t l = 0; l < plan.levels(); ++l) {
+        const uint32_t b = plan.level_begin[l], cnt = plan.level_begin[l + 1] - b;
+        HIP_TRY(launch_refit_level(c.rb_nodes.as<float4>(), c.rb_prims.as<float4>(), c.S.tri_vidx, c.pos.as<float4>(),
+                                   slots + b, cnt, st));
+        launches += cnt ? 1u : 0u;
+    }
+    HIP_TRY(hipEventRecord(c.rb_ev[1], st));
+    float root[32], box[6];
+    HIP_TRY(hipMemcpyAsync(root, c.rb_nodes.p, sizeof(root), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    refit_root_box(root, box);
+    // ---- success: the new tree replaces the old one
+    auto swap_buf = [](DevBuf &a, DevBuf &b) {
+        std::swap(a.p, b.p);
+        std::swap(a.bytes, b.bytes);
+    };
+    swap_buf(c.nodes, c.rb_nodes);
+    swap_buf(c.prims, c.rb_prims);
+    swap_buf(c.refit_slots, c.rb_slots);
+    c.refit = std::move(plan);
+    c.S.nodes = c.nodes.as<float4>();
+    c.S.prims = c.prims.as<float4>();
+    c.S.num_nodes = N;
+    c.bvh_nodes = N;
+    c.bvh_depth = depth;
+    c.stack = stack;
+    c.scene_bytes = 128 * (size_t)N + 48 * (size_t)n;
+    for (int k = 0; k < 3; ++k) c.S.root_min[k] = box[k], c.S.root_max[k] = box[3 + k];
+    if (stats) {
+        std::memset(stats, 0, sizeof(*stats));
+        HIP_TRY(hipEventElapsedTime(&stats->ms_device, c.rb_ev[0], c.rb_ev[1]));
+        stats->nodes = N;
+        stats->depth = depth;
+        stats->stack = (uint32_t)stack;
+        stats->levels = c.refit.levels();
+        stats->launches = launches;
+        stats->ms = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+    return NORI_OK;
+}
+
 int bvh_read(nori_gpu_ctx &c, float *nodes, float *prims, uint32_t *counts) {
     HIP_TRY(hipSetDevice(c.device));
     if (counts) counts[0] = c.S.num_nodes, counts[1] = c.S.num_prims;
@@ -2552,6 +2730,41 @@ int nori_scene_bvh_refit(const nori_scene_desc *d, const float *positions, float
         DeviceBvh bvh;
         build_device_bvh(*d, rmin, rmax, bvh);
         if (positions) refit_host(bvh, build_refit_plan(bvh), prim_vertex_ids(*d), positions, nullptr);
+        if (nodes) std::memcpy(nodes, bvh.nodes.data(), bvh.nodes.size() * 4);
+        if (prims) std::memcpy(prims, bvh.prims.data(), bvh.prims.size() * 4);
+        if (root_box) refit_root_box(bvh.nodes.data(), root_box);
+        return NORI_OK;
+    });
+}
+
+int nori_gpu_rebuild_bvh(nori_gpu_ctx *c, const nori_gpu_rebuild_desc *rd, nori_gpu_rebuild_stats *stats) {
+    return guarded([&] {
+        if (!c || !rd) return fail(NORI_ERR_INVALID, "null argument");
+        return rebuild_bvh(*c, *rd, stats);
+    });
+}
+
+int nori_scene_bvh_rebuild(const nori_scene_desc *d, const float *positions, uint32_t leaf_max,
+                           const float *refit_positions, nori_bvh_rebuild_info *info, float *nodes, float *prims,
+                           float *root_box) {
+    return guarded([&] {
+        if (!d) return fail(NORI_ERR_INVALID, "null argument");
+        if (d->abi_version != NORI_GPU_ABI_VERSION) return fail(NORI_ERR_INVALID, "ABI version mismatch");
+        if (leaf_max > kRebuildLeafMax) return fail(NORI_ERR_INVALID, "nori_scene_bvh_rebuild: leaf_max above 64");
+        for (const float *p : {positions, refit_positions})
+            if (p)
+                for (size_t i = 0; i < 3 * (size_t)d->num_vertices; ++i)
+                    if (!std::isfinite(p[i])) return fail(NORI_ERR_INVALID, "nori_scene_bvh_rebuild: a non-finite position");
+        DeviceBvh bvh;
+        rebuild_host(*d, positions, leaf_max, bvh);
+        if (refit_positions) refit_host(bvh, build_refit_plan(bvh), prim_vertex_ids(*d), refit_positions, nullptr);
+        if (info) {
+            std::memset(info, 0, sizeof(*info));
+            info->device_nodes = bvh.num_nodes;
+            info->depth = bvh.depth;
+            info->num_prims = (uint32_t)(bvh.prims.size() / 12);
+            info->leaf_max = leaf_max ? leaf_max : kRebuildLeafDefault;
+        }
         if (nodes) std::memcpy(nodes, bvh.nodes.data(), bvh.nodes.size() * 4);
         if (prims) std::memcpy(prims, bvh.prims.data(), bvh.prims.size() * 4);
         if (root_box) refit_root_box(bvh.nodes.data(), root_box);

@@ -27,7 +27,7 @@ from ._abi import NoriError, check, lib  # noqa: F401
 __all__ = ["load_scene", "Scene", "GpuRenderer", "RenderThread", "NoriError", "device_count",
            "develop", "write_exr", "write_png", "read_exr", "film_variance", "ldr_bytes", "variance_gray",
            "denoise", "read_image", "block_error", "film_features", "denoise_guided", "film_denoise_guided",
-           "scene_surface", "bvh_refit"]
+           "scene_surface", "bvh_refit", "bvh_rebuild"]
 
 
 def _fptr(a):
@@ -318,6 +318,36 @@ def bvh_refit(scene, positions=None):
     check(lib().nori_scene_bvh_refit(scene.desc_ptr, None if p is None else _fptr(p), _fptr(nodes), _fptr(prims),
                                      _fptr(box)))
     return nodes, prims, box
+
+
+def bvh_rebuild(scene, positions=None, leaf_max=0, refit_positions=None):
+    """The linear BVH of the scene's primitives at `positions` ((num_vertices, 3) float32; None: the
+    scene's own) with leaves of at most `leaf_max` records (1 .. 64; 0: the default, 4), built on
+    the host -- nori_scene_bvh_rebuild, where the rebuild is stated; no GPU needed.  With
+    `refit_positions` the finished tree is then refitted to them as bvh_refit states.  Returns
+    (nodes (n, 32), prims (p, 12), root_box (6,), info dict: device_nodes, depth, num_prims,
+    leaf_max): the arrays GpuRenderer.bvh_nodes() returns after update_vertices(positions) and
+    rebuild_bvh(leaf_max), byte for byte."""
+    nv = scene.desc.num_vertices
+
+    def arg(a, what):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.shape != (nv, 3):
+            raise ValueError(f"{what} {a.shape}: expected {(nv, 3)}")
+        return a
+
+    p, q = arg(positions, "positions"), arg(refit_positions, "refit_positions")
+    pp, qq = (None if a is None else _fptr(a) for a in (p, q))
+    info = _abi.BvhRebuildInfo()
+    check(lib().nori_scene_bvh_rebuild(scene.desc_ptr, pp, leaf_max, qq, C.byref(info), None, None, None))
+    nodes = np.zeros((info.device_nodes, 32), np.float32)
+    prims = np.zeros((info.num_prims, 12), np.float32)
+    box = np.zeros(6, np.float32)
+    check(lib().nori_scene_bvh_rebuild(scene.desc_ptr, pp, leaf_max, qq, C.byref(info), _fptr(nodes), _fptr(prims),
+                                       _fptr(box)))
+    return nodes, prims, box, {k: getattr(info, k) for k in ("device_nodes", "depth", "num_prims", "leaf_max")}
 
 
 class ScanInfo(C.Structure):
@@ -639,6 +669,20 @@ class GpuRenderer:
         st = _abi.UpdateStats()
         check(lib().nori_gpu_update_vertices(self._h, C.byref(ud), C.byref(st)))
         del keep_p, keep_n
+        return st.as_dict()
+
+    def rebuild_bvh(self, leaf_max=0):
+        """Rebuild the context's BVH on the device for the vertex positions it holds now
+        (nori_gpu_rebuild_bvh): a linear BVH with leaves of at most `leaf_max` records (1 .. 64;
+        0: the default, 4), byte for byte bvh_rebuild(scene, positions, leaf_max).  Call it after
+        update_vertices has moved the geometry far from where the current tree was built (a refit
+        keeps that tree's topology); later update_vertices calls refit the rebuilt tree.  Scan-mode
+        and photonmapper contexts raise NoriError (unsupported) with nothing changed.  Returns the
+        stats as a dict: ms, ms_device, nodes, depth, stack, levels, launches."""
+        rd = _abi.RebuildDesc()
+        rd.leaf_max = leaf_max
+        st = _abi.RebuildStats()
+        check(lib().nori_gpu_rebuild_bvh(self._h, C.byref(rd), C.byref(st)))
         return st.as_dict()
 
     def bvh_nodes(self):

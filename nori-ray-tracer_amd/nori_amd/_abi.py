@@ -154,6 +154,24 @@ class UpdateStats(C.Structure):
                 "launches": self.launches}
 
 
+class BvhRebuildInfo(C.Structure):
+    """nori_bvh_rebuild_info: the sizes of nori_scene_bvh_rebuild's tree."""
+    _fields_ = [("device_nodes", C.c_uint32), ("depth", C.c_uint32), ("num_prims", C.c_uint32),
+                ("leaf_max", C.c_uint32), ("reserved", C.c_uint32 * 4)]
+
+
+class RebuildDesc(C.Structure):
+    _fields_ = [("leaf_max", C.c_uint32), ("reserved", C.c_uint32 * 7)]
+
+
+class RebuildStats(C.Structure):
+    _fields_ = [("ms", C.c_float), ("ms_device", C.c_float), ("nodes", C.c_uint32), ("depth", C.c_uint32),
+                ("stack", C.c_uint32), ("levels", C.c_uint32), ("launches", C.c_uint32), ("reserved", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
 # exported entry points: name -> (restype, argtypes)
 SIGNATURES = {
     "nori_gpu_last_error": (C.c_char_p, []),
@@ -197,6 +215,10 @@ SIGNATURES = {
     "nori_gpu_bvh_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint32)]),
     "nori_scene_bvh_refit": (C.c_int, [C.POINTER(SceneDesc), C.POINTER(C.c_float), C.POINTER(C.c_float),
                                        C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "nori_scene_bvh_rebuild": (C.c_int, [C.POINTER(SceneDesc), C.POINTER(C.c_float), C.c_uint32, C.POINTER(C.c_float),
+                                         C.POINTER(BvhRebuildInfo), C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                         C.POINTER(C.c_float)]),
+    "nori_gpu_rebuild_bvh": (C.c_int, [C.c_void_p, C.POINTER(RebuildDesc), C.POINTER(RebuildStats)]),
     "nori_gpu_cancel": (C.c_int, [C.c_void_p]),
     "nori_gpu_progress": (C.c_float, [C.c_void_p]),
     "nori_gpu_destroy": (None, [C.c_void_p]),
@@ -215,7 +237,7 @@ SIGNATURES = {
 
 # entry points added without an ABI bump (no existing signature or struct changed)
 ADDED_IN_7 = {"nori_gpu_query", "nori_scene_surface", "nori_gpu_camera_rays", "nori_gpu_update_vertices",
-              "nori_gpu_bvh_read", "nori_scene_bvh_refit"}
+              "nori_gpu_bvh_read", "nori_scene_bvh_refit", "nori_scene_bvh_rebuild", "nori_gpu_rebuild_bvh"}
 
 COMM_ID_BYTES = 128
 SHARD_PASSES, SHARD_BLOCKS = 0, 1
