@@ -441,8 +441,10 @@ typedef struct nori_gpu_stats {
     double ms_scan_rtc;
     /* 1 when the shade kernel traced its own next-event shadow rays instead of
        queueing them for k_shadow (scan-mode scenes with the basic plugins by
-       default; NORI_NEE_INLINE=0/1 at nori_gpu_create) */
-    uint32_t nee_inline, reserved0;
+       default; NORI_NEE_INLINE=0/1 at nori_gpu_create), and 1 when it also
+       traced each vertex's extension ray itself instead of reading the hit of
+       a separate extension launch (the same scenes; NORI_EXT_INLINE=0/1) */
+    uint32_t nee_inline, ext_inline;
 } nori_gpu_stats;
 
 typedef struct nori_gpu_hit {

@@ -95,6 +95,10 @@ struct DevScene {
     // (kernels.hip k_shade) instead of queueing them for k_shadow_scan
     // (nori_gpu_create: NORI_NEE_INLINE=0 keeps the queue)
     int32_t nee_inline;
+    // ... and the closest hit of the vertex it shades (k_shade scans the
+    // queued ray itself instead of reading the hit k_extend_scan wrote; only
+    // with nee_inline, basic plugins; nori_gpu_create: NORI_EXT_INLINE=0 / 1)
+    int32_t ext_inline;
     float root_min[3], root_max[3];  // scene box = BVH root box (bvh.cpp:345)
     int32_t W, H;
     float invW, invH;

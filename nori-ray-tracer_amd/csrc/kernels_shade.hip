@@ -19,6 +19,31 @@ constexpr uint32_t kSlotEmit = 1u << 31, kSlotEm = 1u << 30;  // above kWorkMask
 #ifndef NORI_SORT_OCTANT
 #define NORI_SORT_OCTANT 1
 #endif
+// S.ext_inline (basic-plugin kernels, VAR == 0): the closest hit of the
+// thread's queued ray through the wave-uniform scan, as extend_scan_body finds
+// it -- the ray of path_ray (load_path computes the same mint, maxt), a wave
+// whose live lanes are all camera rays through the in-plane filter, every
+// other wave unchecked; both scans are exact per ray, so the hit does not
+// depend on the wave's composition.  live: the lane holds a path; the others
+// run the arithmetic on their stale entry and touch no memory (the records
+// arrive through scalar loads).
+// The scan stands after the blob is staged and the barrier taken: against
+// the blob's loads held in registers across the scan, and against the scan
+// before those loads are issued, that order measured fastest (DESIGN.md
+// section 5).
+ND float4 ext_scan(const DevScene &Sg, const PathState &ps, bool is_live) {
+    TRay r[1];
+    r[0].o = ps.o;
+    r[0].d = ps.d;
+    r[0].mint = ps.mint;
+    r[0].maxt = ps.maxt;
+    bool live[1] = {is_live}, f[1];
+    float t[1], u[1], v[1];
+    uint32_t p[1];
+    if (Sg.camera_cull && Sg.plane_f && __all(!is_live || ps.cam)) scan_rays<1, false, 2>(Sg, r, live, t, p, u, v, f);
+    else scan_rays<1, false, 0>(Sg, r, live, t, p, u, v, f);
+    return make_float4(t[0], __uint_as_float(p[0]), u[0], v[0]);
+}
 // lds_bytes != 0: the scene blob is staged into LDS first, so the chains of
 // dependent table reads of a vertex (shape -> bsdf -> vertices -> light CDF)
 // run at LDS instead of L2 latency.
@@ -80,7 +105,11 @@ void k_shade(ShadeArgs args) {
     const uint4 st0 = seg.stats[b];
     PathState ps;
     load_path(Sg, wd, in, q, ps);
-    const float4 hit = in.hit[q];
+    const bool ext_in = VAR == 0 && Sg.ext_inline != 0;
+    float4 hit = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (!ext_in) hit = in.hit[q];
+    // (a wave without a live lane scans nothing; the wave index made scalar)
+    const bool ext_wave = ext_in && (uint32_t)__builtin_amdgcn_readfirstlane((int)wave) * 64u < n_in;
     // The next kSeg positions of the segment's work stream and their pixels:
     // slot j of the free slots regenerates position cursor + j.  Looked up
     // here, beside the path loads, and parked in LDS; a lookup after the
@@ -94,6 +123,8 @@ void k_shade(ShadeArgs args) {
         __syncthreads();
         S = scene_in_lds(Sg, reinterpret_cast<const char *>(blob_lds));
     }
+    if constexpr (VAR == 0)
+        if (ext_wave) hit = ext_scan(Sg, ps, tid < n_in);
     NORI_SPHASE(0)
     ShadowOut so;
     so.emit = false;

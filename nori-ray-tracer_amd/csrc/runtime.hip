@@ -1014,6 +1014,12 @@ void upload_scene(nori_gpu_ctx &c, const nori_scene_desc &d) {
         // shade kernel carries it (the basic ones; kernels.h kNeeFull).
         const char *n = std::getenv("NORI_NEE_INLINE");
         S.nee_inline = c.stack == 0 && (n ? n[0] == '1' : S.basic != 0) && (S.basic != 0 || kNeeFull);
+        // ... and each vertex's extension ray (k_shade's closest-hit scan in
+        // place of the extension launch and the hit's round trip through
+        // memory): scan-mode scenes with the basic plugins and the inline
+        // shadow rays.  NORI_EXT_INLINE=0 / 1 forces it off / on there.
+        const char *x = std::getenv("NORI_EXT_INLINE");
+        S.ext_inline = c.stack == 0 && S.basic != 0 && S.nee_inline != 0 && (x ? x[0] == '1' : true);
     }
     {
         // one launch for an iteration's extension and shadow queues: on for
@@ -1107,9 +1113,12 @@ bool debug_log() {
 // 3 parts 651, 4 parts 499 Msamples/s -- 4 streams exceed the hardware
 // queues; table scene 517 -> 555; C2 4563 -> 4658; 64-spp share 3026 ->
 // 3089; C4 and C5 within 1 %).
-uint32_t pool_parts(bool bvh) {
-    (void)bvh;
-    const uint32_t def = 3u;
+// Renders whose shade kernel traces its own extension rays (ext_loop): 2.
+// An iteration is one launch there, so no part's scan is left to slip under
+// another part's shade launch (C2, 1M pool: 2 parts 6529-6637 Msamples/s;
+// 2M pool: 1 part 5579-5615, 2 parts 6404-6460, 3 parts 6311-6410).
+uint32_t pool_parts(bool ext_loop) {
+    const uint32_t def = ext_loop ? 2u : 3u;
     const char *e = std::getenv("NORI_POOL_PARTS");
     const long v = e ? std::atol(e) : (long)def;
     return (uint32_t)(v >= 1 && v <= kMaxParts ? v : def);
@@ -1368,8 +1377,19 @@ int render(nori_gpu_ctx &c, const nori_gpu_render_desc &rd, float *rgbw_out, nor
     // 1.25M, 4555 at 768K; 3 reps), so the floor is 1M.  The BVH walks
     // (C3) want about 1/8 in flight: 4M 846-851 against 807-812 at 2M
     // (3M 796-798, 6M 796-798, 8M 839-846; 3 interleaved reps).
+    // Renders whose shade kernel traces its own extension rays (ext_loop)
+    // keep the 1M floor at every size: with one launch per iteration the
+    // smaller pool wins (C2 at 512 spp, two parts: 1M 6529-6637, 1.5M
+    // 6501-6511, 2M 6404-6460, 3M 6103-6210, 4M 6172-6180 Msamples/s; the
+    // 64-spp share: 768K 4926-4981, 1M 5054-5131, 1.5M 4884-4998).
     if (one_bounce) return render_one_bounce(c, rd, pixels, blocks, rgbw_out, stats, t0);
     if (M > kWorkMask) throw NoriException(NORI_ERR_INVALID, "frame too large: more than 2^29 pixels per pass");
+    const bool timing = rd.timing != 0;
+    // S.ext_inline: an iteration is the shade launch alone.  A timing render
+    // keeps the two launches (one event span per kernel), so its shade kernel
+    // reads the hits as without the flag, and it keeps the pool and the parts
+    // of the two-launch loop.
+    const bool ext_loop = S.ext_inline != 0 && !timing;
     uint32_t pool = rd.path_pool;
     if (!pool) {  // NORI_PATH_POOL: default pool size override (tuning)
         const char *e = std::getenv("NORI_PATH_POOL");
@@ -1378,7 +1398,7 @@ int render(nori_gpu_ctx &c, const nori_gpu_render_desc &rd, float *rgbw_out, nor
         } else {
             const uint64_t want = (uint64_t)passes * M / (c.stack ? 8 : 16);
             pool = 1u << 20;
-            while (pool < (1u << 22) && pool < want) pool <<= 1;
+            while (!ext_loop && pool < (1u << 22) && pool < want) pool <<= 1;
         }
     }
     pool = std::max<uint32_t>(kSeg, (pool + kSeg - 1) / kSeg * kSeg);
@@ -1422,7 +1442,8 @@ int render(nori_gpu_ctx &c, const nori_gpu_render_desc &rd, float *rgbw_out, nor
         int kind;
     };
     std::vector<Span> spans;
-    const bool timing = rd.timing != 0;
+    DevScene Sk = S;
+    if (!ext_loop) Sk.ext_inline = 0;
     auto timed_on = [&](hipStream_t st, int kind, auto &&launch) {
         if (!timing) {
             HIP_TRY(launch());
@@ -1436,7 +1457,7 @@ int render(nori_gpu_ctx &c, const nori_gpu_render_desc &rd, float *rgbw_out, nor
     };
     auto timed = [&](int kind, auto &&launch) { timed_on(c.stream, kind, launch); };
     bool cancelled = false;
-    const uint32_t parts = std::max<uint32_t>(1, std::min<uint32_t>(pool_parts(c.stack != 0), pool / kSeg));
+    const uint32_t parts = std::max<uint32_t>(1, std::min<uint32_t>(pool_parts(ext_loop), pool / kSeg));
     const uint32_t G = pool / kSeg;
     SegState seg{{c.seg[0].as<uint32_t>(), c.seg[1].as<uint32_t>()}, c.seg[2].as<uint32_t>(), c.seg[3].as<uint32_t>(),
                  c.segstats.as<uint4>()};
@@ -1500,11 +1521,12 @@ int render(nori_gpu_ctx &c, const nori_gpu_render_desc &rd, float *rgbw_out, nor
                 hipStream_t st = h ? c.parts[h] : c.stream;
                 const SegState &sg = segh[h];
                 timed_on(st, 2, [&] {
-                    return launch_shade(S, Qh[h][in], Qh[h][out], sqh[h], sg, in, wdh[h], c.rec.as<float4>(), C,
+                    return launch_shade(Sk, Qh[h][in], Qh[h][out], sqh[h], sg, in, wdh[h], c.rec.as<float4>(), C,
                                         Gp[h], st);
                 });
                 hipError_t both_err = hipSuccess;
                 if (S.nee_inline) {  // the shadow rays were traced by k_shade itself
+                    if (ext_loop) continue;  // ... and so will the next vertex's extension ray be
                     timed_on(st, 0, [&] { return launch_extend(S, Qh[h][out], sg.cnt[out], Gp[h], c.stack, st, &c.rtc); });
                     continue;
                 }
@@ -1549,6 +1571,11 @@ int render(nori_gpu_ctx &c, const nori_gpu_render_desc &rd, float *rgbw_out, nor
                 }
             }
         }
+        // ext_loop: the last iteration's survivors and new samples have no hits
+        // yet; the finisher below reads them, so they are traced once here
+        for (uint32_t h = 0; ext_loop && !cancelled && h < parts; ++h)
+            HIP_TRY(launch_extend(S, Qh[h][last_out], segh[h].cnt[last_out], Gp[h], c.stack, h ? c.parts[h] : c.stream,
+                                  &c.rtc));
         for (uint32_t h = 1; h < parts; ++h) {  // join: the tail below runs on the whole pool
             HIP_TRY(hipEventRecord(c.joins[h], c.parts[h]));
             HIP_TRY(hipStreamWaitEvent(c.stream, c.joins[h], 0));
@@ -1679,6 +1706,7 @@ int render(nori_gpu_ctx &c, const nori_gpu_render_desc &rd, float *rgbw_out, nor
         stats->scan_rtc_cached = c.rtc.cached ? 1u : 0u;
         stats->ms_scan_rtc = c.rtc.compile_ms;
         stats->nee_inline = S.nee_inline ? 1u : 0u;
+        stats->ext_inline = S.ext_inline ? 1u : 0u;
     }
     if (cancelled) return fail(NORI_ERR_CANCELLED, "rendering was cancelled");
     return NORI_OK;

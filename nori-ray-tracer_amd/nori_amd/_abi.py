@@ -118,7 +118,7 @@ class Stats(C.Structure):
                 ("ms_extend", C.c_double), ("ms_shadow", C.c_double), ("ms_shade", C.c_double),
                 ("ms_splat", C.c_double), ("ms_finish", C.c_double),
                 ("scan_rtc", C.c_uint32), ("scan_rtc_cached", C.c_uint32), ("ms_scan_rtc", C.c_double),
-                ("nee_inline", C.c_uint32), ("reserved0", C.c_uint32)]
+                ("nee_inline", C.c_uint32), ("ext_inline", C.c_uint32)]
 
     def as_dict(self):
         return {f: getattr(self, f) for f, _ in self._fields_}
