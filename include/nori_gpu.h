@@ -50,6 +50,9 @@
  *                         (dynamic geometry: a linear BVH built on the device
  *                          for the positions as they are now; no reference
  *                          counterpart)
+ *   nori_scene_scan_rtc, nori_scene_shade_rtc, nori_gpu_shade_rtc_info
+ *                         (the scene-specialised kernels compiled at context
+ *                          creation through hipRTC; no reference counterpart)
  *   nori_gpu_comm_*, nori_gpu_render_sharded
  *                         <- the same pass loop spread over the GPUs of a node,
  *                            one process per GPU; the cross-GPU film merge is
@@ -396,6 +399,16 @@ int nori_scene_scan_list(const nori_scene_desc *scene, nori_scan_info *info, flo
  * NORI_ERR_UNSUPPORTED when hipRTC is missing or the compile fails
  * (nori_gpu_last_error holds the log). */
 int nori_scene_scan_rtc(const nori_scene_desc *scene, const char *arch, size_t *code_bytes, double *ms);
+
+/* Compiles the scene's own shade kernel (the second hipRTC program of
+ * nori_gpu_create, rtc.hip: the wavefront loop's k_shade for the scene's
+ * integrator with the scan list as literals, so that the extension and shadow
+ * scans inside it need no loads) for the target `arch`, without a device.
+ * Only scan-mode scenes with the basic plugin set and a path integrator get
+ * one: *code_bytes = 0 and *ms = 0 for every other scene, which the
+ * library's ahead-of-time kernels serve.  Errors as nori_scene_scan_rtc.
+ * (Added without an ABI bump, like the calls of the BVH rebuild.) */
+int nori_scene_shade_rtc(const nori_scene_desc *scene, const char *arch, size_t *code_bytes, double *ms);
 
 /* ---- GPU context ----------------------------------------------------------- */
 typedef struct nori_gpu_ctx nori_gpu_ctx;
@@ -795,6 +808,16 @@ typedef struct nori_gpu_rebuild_stats {
  * NORI_ERR_INVALID -- a null ctx or desc, leaf_max > 64, reserved != 0.
  * stats may be NULL. */
 int nori_gpu_rebuild_bvh(nori_gpu_ctx *ctx, const nori_gpu_rebuild_desc *desc, nori_gpu_rebuild_stats *stats);
+
+/* The context's own shade kernel (nori_scene_shade_rtc): *active = 1 if
+ * renders launch it in place of the ahead-of-time kernel (0 for BVH and
+ * full-plugin scenes, under NORI_RTC=0 or NORI_RTC_SHADE=0, and after any
+ * failure to compile, load or match its argument layout), *cached = 1 if its
+ * code object came from the process or disk cache, *ms = the compile or cache
+ * read time paid at nori_gpu_create, *code_bytes = the code object's size.
+ * Any output may be null.  nori_gpu_stats keeps its layout: scan_rtc and
+ * ms_scan_rtc there speak of the scan program alone. */
+int nori_gpu_shade_rtc_info(nori_gpu_ctx *ctx, int *active, int *cached, double *ms, size_t *code_bytes);
 /* Introspection for tests, like nori_scene_scan_list: the context's BVH nodes
  * (32 floats per node) and primitive records (12 floats per record, leaf
  * order; a scan-mode context holds its scan list there) as they are on the

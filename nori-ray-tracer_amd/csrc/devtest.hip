@@ -8,6 +8,7 @@
 #include <stdint.h>
 
 #include "bsdf_desc.h"
+#include "kernels.h"
 #include "shading.h"
 
 using namespace nori;

@@ -10,11 +10,11 @@
 #include <string>
 #include <vector>
 
-#include "dev_scene.h"
+#include "kernel_config.h"
 
 namespace nori {
 
-constexpr int kShadeBlock = 256;   // shade / regen work-group size
+// (kShadeBlock, kShadeLdsMax, kNeeFull: kernel_config.h)
 constexpr int kTraceBlock = 128;   // traversal work-group size (LDS stack columns)
 constexpr int kTraceSpill = 64;    // traversal stack entries beyond the LDS part (private memory)
 #ifndef NORI_STACK_KEYS
@@ -32,18 +32,6 @@ constexpr int kScanRays = NORI_SCAN_RAYS;  // rays per thread of the scan-mode e
 #define NORI_SCAN_RAYS_SHADOW 1
 #endif
 constexpr int kScanRaysShadow = NORI_SCAN_RAYS_SHADOW;  // ... and of the scan-mode shadow kernel
-#ifndef NORI_SHADE_LDS_MAX
-#define NORI_SHADE_LDS_MAX 16384
-#endif
-constexpr uint32_t kShadeLdsMax = NORI_SHADE_LDS_MAX;  // largest scene blob the shade kernel stages in LDS
-// The shade kernels of the full plugin set are compiled without the inline
-// shadow rays (S.nee_inline only for basic scenes): with them, C4 3964 and
-// C5 4162 against 4000 / 4308 Msamples/s, queue mode both (one box, 2 reps).
-// NORI_NEE_FULL=1 compiles them in (NORI_NEE_INLINE=1 then applies there too).
-#ifndef NORI_NEE_FULL
-#define NORI_NEE_FULL 0
-#endif
-constexpr bool kNeeFull = NORI_NEE_FULL;
 
 struct SplatDesc {
     uint32_t M;               // pixels per pass in the work list
@@ -74,10 +62,31 @@ struct ScanRtc {
     bool cached = false;      // the code object came from the process or disk cache
     size_t code_bytes = 0;
 };
+// The scene's own compilation of k_shade (shade_kernel.h through hipRTC):
+// scan-mode scenes with the basic plugin set, whose k_shade holds the scans.
+struct ShadeRtc {
+    hipModule_t mod = nullptr;
+    hipFunction_t shade = nullptr;  // nori_rtc_shade = k_shade<integrator, lds, 0> with literal records
+    int integrator = 0;
+    bool lds = false;
+    double compile_ms = 0.0;  // hipRTC compile (or cache read) at context creation
+    bool cached = false;
+    size_t code_bytes = 0;
+};
+// Whether contexts use it where it can be built, absent NORI_RTC_SHADE.
+constexpr bool kShadeRtcDefault = true;
 std::string rtc_const_scene(const ScanRtcScene &sc);
-// Compiles (or finds cached) the specialised code object for target `arch`.
+// Compiles (or finds cached) the specialised code object for target `arch`;
+// fresh: the cached copies are dropped first.
 bool rtc_compile(const ScanRtcScene &sc, const std::string &arch, int trace_cull, std::vector<char> &code, double &ms,
-                 bool &cached, std::string &why);
+                 bool &cached, std::string &why, bool fresh = false);
+// ... and the shade program's, for k_shade<integrator, lds, 0>.
+bool rtc_compile_shade(const ScanRtcScene &sc, const std::string &arch, int integrator, bool lds,
+                       std::vector<char> &code, double &ms, bool &cached, std::string &why, bool fresh = false);
+bool shade_rtc_wanted(std::string &why);  // NORI_RTC / NORI_RTC_SHADE
+// Loads it on the current device after checking its ShadeArgs layout; false (with why) leaves `out` empty.
+bool shade_rtc_build(const ScanRtcScene &sc, int device, int integrator, bool lds, ShadeRtc &out, std::string &why);
+void shade_rtc_release(ShadeRtc &r);
 // ... and loads it on the current device; false (with why) leaves `out` empty.
 bool scan_rtc_build(const ScanRtcScene &sc, int device, int trace_cull, ScanRtc &out, std::string &why);
 void scan_rtc_release(ScanRtc &r);
@@ -89,7 +98,14 @@ hipError_t launch_trace(const DevScene &S, const float4 *rays, uint32_t n, int a
                         hipStream_t st, const ScanRtc *rtc = nullptr);
 hipError_t launch_shade(const DevScene &S, const PathQueue &in, const PathQueue &out, const ShadowQueue &sq,
                         const SegState &seg, int in_sel, const WorkDesc &wd, float4 *rec, Counters *C,
-                        uint32_t nseg, hipStream_t st);
+                        uint32_t nseg, hipStream_t st, const ShadeRtc *rtc = nullptr);
+// The blob size up to which launch_shade stages the scene in LDS (the LDS
+// template argument, and the one the scene's ShadeRtc is compiled with).
+// The integrator k_shade is instantiated for (launch_shade's switch).
+inline int shade_integrator(int i) {
+    return i == NORI_INTEGRATOR_PATH_MATS || i == NORI_INTEGRATOR_VOLUMETRIC ? i : (int)NORI_INTEGRATOR_PATH_MIS;
+}
+inline uint32_t shade_lds_bytes(uint32_t blob_bytes) { return blob_bytes <= kShadeLdsMax ? blob_bytes : 0u; }
 hipError_t launch_extend(const DevScene &S, const PathQueue &q, const uint32_t *cnt, uint32_t G, int stack,
                          hipStream_t st, const ScanRtc *rtc = nullptr);
 hipError_t launch_shadow(const DevScene &S, const ShadowQueue &sq, const uint32_t *shcnt, float4 *rec, uint32_t G,

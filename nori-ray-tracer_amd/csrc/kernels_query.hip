@@ -4,6 +4,7 @@
 // nori_gpu_camera_rays in nori_gpu.h).
 #include <cstdlib>
 
+#include "kernels.h"
 #include "shading.h"
 
 namespace nori {

@@ -210,6 +210,7 @@ struct nori_gpu_ctx {
     hipEvent_t joins[kMaxParts] = {};
     DevScene S{};
     ScanRtc rtc;         // scan-mode scenes: the scan kernels specialised for this scene (rtc.hip), or empty
+    ShadeRtc shade_rtc;  // ... with the basic plugins: k_shade compiled for this scene (rtc.hip), or empty
     // an iteration's extension and shadow rays of a part in one launch
     // (launch_trace_both); set at upload_scene (NORI_TRACE_FUSE=0 / 1 forces it)
     bool fuse_trace = true;
@@ -280,6 +281,7 @@ struct nori_gpu_ctx {
             if (parts[h]) (void)hipStreamDestroy(parts[h]);
         }
         scan_rtc_release(rtc);
+        shade_rtc_release(shade_rtc);
         for (auto e : q_ev)
             if (e) (void)hipEventDestroy(e);
         for (auto e : upd_ev)
@@ -692,6 +694,31 @@ template <class Vtx> float mesh_area_cdf(const uint32_t *tri, uint32_t count, Vt
     return norm;
 }
 
+// The size of the small-scene blob upload_scene builds (its ten tables, each
+// 16-byte aligned), from the description alone: nori_scene_shade_rtc chooses
+// the shade kernel's LDS variant with it, without a device.
+size_t scene_blob_bytes(const nori_scene_desc &d, size_t prim_floats, size_t node_floats) {
+    size_t prims = 0, cdf = 0;
+    for (uint32_t s = 0; s < d.num_shapes; ++s) {
+        const bool mesh = d.shapes[s].type == NORI_SHAPE_MESH;
+        prims += mesh ? d.shapes[s].tri_count : 1u;
+        cdf += mesh ? (size_t)d.shapes[s].tri_count + 1 : 0u;
+    }
+    const size_t vtx = d.num_vertices ? d.num_vertices : 1u;
+    const size_t parts[10] = {prim_floats * 4, prims * 12, vtx * 16, vtx * 16, prims * 4, d.num_shapes * sizeof(DevShape),
+                              d.num_bsdfs * sizeof(DevBsdf), d.num_emitters * sizeof(DevEmitter), (cdf ? cdf : 1u) * 4,
+                              node_floats * 4};
+    size_t n = 0;
+    for (size_t b : parts) n = (n + 15) / 16 * 16 + b;
+    return (n + 15) / 16 * 16;
+}
+// Scenes whose k_shade can hold a scan, and so get a compilation of their own
+// (rtc.hip): scan mode with a scan list the scan program takes, the basic
+// plugin set, an integrator of the wavefront loop.
+bool shade_rtc_scene(const nori_scene_desc &d, bool scan, size_t records) {
+    return scan && records <= 2 * kScanMaxPrims && basic_scene(d) && d.integrator < NORI_INTEGRATOR_NORMALS;
+}
+
 void upload_scene(nori_gpu_ctx &c, const nori_scene_desc &d) {
     float rmin[3] = {__builtin_inff(), __builtin_inff(), __builtin_inff()};
     float rmax[3] = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
@@ -1039,6 +1066,19 @@ void upload_scene(nori_gpu_ctx &c, const nori_scene_desc &d) {
     if (S.border > 4) throw NoriException(NORI_ERR_UNSUPPORTED, "filter radius above 4.5 pixels");
     S.jit_lk = jit_code_lookup(S.filter_radius, S.lookup);
     S.integrator = d.integrator;
+    if (shade_rtc_scene(d, scan, scan_list.prims.size() / 12)) {  // k_shade compiled for this scene (after the scan program)
+        ScanRtcScene sc{scan_list.prims.data(), (uint32_t)(scan_list.prims.size() / 12), scan_list.plane_c.data(),
+                        scan_list.plane_f.data(), (uint32_t)scan_list.plane_c.size(),
+                        {scan_list.plane_end[0], scan_list.plane_end[1], scan_list.plane_end[2]}, scan_list.tris,
+                        scan_list.real};
+        std::string why;
+        if (!shade_rtc_build(sc, c.device, shade_integrator(S.integrator), shade_lds_bytes(S.blob_bytes) != 0,
+                             c.shade_rtc, why) && debug_log())
+            std::fprintf(stderr, "[nori] ahead-of-time shade kernel: %s\n", why.c_str());
+        if (debug_log() && scene_blob_bytes(d, prim_list.size(), bvh.nodes.size()) != blob.size())
+            std::fprintf(stderr, "[nori] scene_blob_bytes %zu != blob %zu\n",
+                         scene_blob_bytes(d, prim_list.size(), bvh.nodes.size()), blob.size());
+    }
     {  // deviation D10 (shading.h skip_nee); NORI_DISCRETE_NEE=1 keeps the full NEE everywhere
         bool env = false;
         for (uint32_t i = 0; i < d.num_emitters; ++i) env = env || d.emitters[i].type == NORI_EMITTER_ENVMAP;
@@ -1086,6 +1126,19 @@ PathQueue queue_of(nori_gpu_ctx &c, int b) {
 constexpr int kRing = 16;     // readback ring entries
 constexpr int kLookahead = 6;    // iterations queued ahead of the termination check
 constexpr int kLookaheadEnd = 2; // ... once work streams run dry
+// NORI_LOOKAHEAD=n (0 .. 8) replaces kLookahead.  The termination check reads
+// the done flag as the device has set it by now, which may be up to `lag`
+// iterations further than the event just waited for: how many iterations a
+// render launches past the one that handed out the last work id (and so how
+// its rays divide between the loop and the finisher) depends on how far the
+// host runs ahead of the device.  With 0 the host waits for every iteration
+// before it reads the flag, and the counts are the same in every run (the
+// tests that compare two renders' statistics exactly use it).
+int lookahead() {
+    const char *e = std::getenv("NORI_LOOKAHEAD");
+    const int v = e ? std::atoi(e) : kLookahead;
+    return v < 0 ? 0 : v > 8 ? 8 : v;
+}
 
 struct Timers {
     std::vector<hipEvent_t> ev;
@@ -1504,7 +1557,7 @@ int render(nori_gpu_ctx &c, const nori_gpu_render_desc &rd, float *rgbw_out, nor
         }
         HIP_TRY(hipEventRecord(c.fork, c.stream));  // the part streams start after the resets above
         for (uint32_t h = 1; h < parts; ++h) HIP_TRY(hipStreamWaitEvent(c.parts[h], c.fork, 0));
-        uint64_t lag = kLookahead;
+        uint64_t lag = (uint64_t)lookahead();
         // NORI_DEBUG: host time spent enqueuing vs waiting on the ring events
         // (a wait that returns at once means the device ran dry of work)
         const bool dbg = debug_log();
@@ -1522,7 +1575,7 @@ int render(nori_gpu_ctx &c, const nori_gpu_render_desc &rd, float *rgbw_out, nor
                 const SegState &sg = segh[h];
                 timed_on(st, 2, [&] {
                     return launch_shade(Sk, Qh[h][in], Qh[h][out], sqh[h], sg, in, wdh[h], c.rec.as<float4>(), C,
-                                        Gp[h], st);
+                                        Gp[h], st, &c.shade_rtc);
                 });
                 hipError_t both_err = hipSuccess;
                 if (S.nee_inline) {  // the shadow rays were traced by k_shade itself
@@ -2579,6 +2632,48 @@ int nori_scene_scan_rtc(const nori_scene_desc *d, const char *arch, size_t *code
         std::string why;
         if (!rtc_compile(sc, arch, 1, code, *ms, cached, why)) return fail(NORI_ERR_UNSUPPORTED, why);
         *code_bytes = code.size();
+        return NORI_OK;
+    });
+}
+int nori_scene_shade_rtc(const nori_scene_desc *d, const char *arch, size_t *code_bytes, double *ms) {
+    return guarded([&] {
+        if (!d || !arch || !code_bytes || !ms) return fail(NORI_ERR_INVALID, "null argument");
+        if (d->abi_version != NORI_GPU_ABI_VERSION) return fail(NORI_ERR_INVALID, "ABI version mismatch");
+        float rmin[3], rmax[3];
+        scene_root_box(*d, rmin, rmax);
+        DeviceBvh bvh;
+        build_device_bvh(*d, rmin, rmax, bvh);
+        const uint32_t n = (uint32_t)(bvh.prims.size() / 12);
+        *code_bytes = 0;
+        *ms = 0.0;
+        // (the traversal as nori_gpu_create chooses it, NORI_TRAVERSAL included)
+        const char *mode = std::getenv("NORI_TRAVERSAL");
+        bool scan = n <= kScanMaxPrims;
+        if (mode && std::string(mode) == "bvh") scan = false;
+        if (mode && std::string(mode) == "scan") scan = true;
+        if (!scan) return NORI_OK;
+        const ScanList L = build_scan_list(bvh, n);
+        if (!shade_rtc_scene(*d, scan, L.prims.size() / 12)) return NORI_OK;  // the ahead-of-time kernel serves it
+        ScanRtcScene sc{L.prims.data(), (uint32_t)(L.prims.size() / 12), L.plane_c.data(), L.plane_f.data(),
+                        (uint32_t)L.plane_c.size(), {L.plane_end[0], L.plane_end[1], L.plane_end[2]}, L.tris, L.real};
+        const size_t blob = scene_blob_bytes(*d, L.prims.size(), bvh.nodes.size());
+        const bool lds = blob <= kBlobMaxBytes && shade_lds_bytes((uint32_t)blob) != 0;
+        std::vector<char> code;
+        bool cached = false;
+        std::string why;
+        if (!rtc_compile_shade(sc, arch, shade_integrator(d->integrator), lds, code, *ms, cached, why))
+            return fail(NORI_ERR_UNSUPPORTED, why);
+        *code_bytes = code.size();
+        return NORI_OK;
+    });
+}
+int nori_gpu_shade_rtc_info(nori_gpu_ctx *c, int *active, int *cached, double *ms, size_t *code_bytes) {
+    return guarded([&] {
+        if (!c) return fail(NORI_ERR_INVALID, "null argument");
+        if (active) *active = c->shade_rtc.shade ? 1 : 0;
+        if (cached) *cached = c->shade_rtc.cached ? 1 : 0;
+        if (ms) *ms = c->shade_rtc.compile_ms;
+        if (code_bytes) *code_bytes = c->shade_rtc.code_bytes;
         return NORI_OK;
     });
 }

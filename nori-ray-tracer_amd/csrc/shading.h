@@ -4,8 +4,12 @@
 // shade_vertex / shade_vertex_vol, the glass-sphere chord code and the
 // per-sample film splat of the finisher.  Device code for the .hip units.
 #pragma once
-#include "kernels.h"
+#include "kernel_config.h"
 #include "scan.h"
+
+#if defined(__HIPCC_RTC__) && !defined(M_PI)  // (hipRTC has no <math.h>: glibc's value)
+#define M_PI 3.14159265358979323846
+#endif
 
 namespace nori {
 

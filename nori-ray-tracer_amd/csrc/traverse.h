@@ -9,11 +9,7 @@
 
 namespace nori {
 
-// ------------------------------------------------------------------ wave helpers
-ND uint32_t lane_id() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
-ND uint32_t rank_in(uint64_t mask) {  // set lanes of `mask` below this lane
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-}
+// (the wave helpers lane_id and rank_in: kernel_config.h)
 
 // ------------------------------------------------------------------ traversal
 // Load through the global address space: the scene tables sit in a struct

@@ -377,6 +377,16 @@ def scan_rtc(scene, arch="gfx950"):
     return n.value, ms.value
 
 
+def shade_rtc(scene, arch="gfx950"):
+    """Compile the scene's own shade kernel for `arch` (the second hipRTC program GpuRenderer loads:
+    k_shade for the scene's integrator with the scan list as literals; no device needed): (code
+    object bytes, milliseconds); (0, 0.0) for a scene the ahead-of-time kernels serve (BVH
+    traversal, the full plugin set, a one-bounce integrator)."""
+    n, ms = C.c_size_t(), C.c_double()
+    check(lib().nori_scene_shade_rtc(scene.desc_ptr, arch.encode(), C.byref(n), C.byref(ms)))
+    return n.value, ms.value
+
+
 def read_exr(path):
     """R, G, B planes of an OpenEXR file as a (height, width, 3) float32 array (nori_read_exr)."""
     w, h = C.c_int(), C.c_int()
@@ -425,6 +435,15 @@ class GpuRenderer:
 
     def __exit__(self, *a):
         self.close()
+
+    @property
+    def shade_rtc(self):
+        """The context's own shade kernel (nori_gpu_shade_rtc_info): {"active": renders launch it in
+        place of the ahead-of-time kernel, "cached": its code object came from the cache, "ms": the
+        compile or cache-read time paid at creation, "code_bytes"}."""
+        a, c, ms, n = C.c_int(), C.c_int(), C.c_double(), C.c_size_t()
+        check(lib().nori_gpu_shade_rtc_info(self._h, C.byref(a), C.byref(c), C.byref(ms), C.byref(n)))
+        return {"active": bool(a.value), "cached": bool(c.value), "ms": ms.value, "code_bytes": n.value}
 
     def render(self, passes=None, pass_begin=0, blocks=None, seed=0, out=None, path_pool=0,
                device_ptr=None, timing=False, variance=None):

@@ -194,6 +194,9 @@ SIGNATURES = {
     "nori_scene_scan_list": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float),
                                        C.POINTER(C.c_float)]),
     "nori_scene_scan_rtc": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_size_t), C.POINTER(C.c_double)]),
+    "nori_scene_shade_rtc": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_size_t), C.POINTER(C.c_double)]),
+    "nori_gpu_shade_rtc_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double),
+                                          C.POINTER(C.c_size_t)]),
     "nori_gpu_device_count": (C.c_int, [C.POINTER(C.c_int)]),
     "nori_gpu_create": (C.c_int, [C.POINTER(SceneDesc), C.c_int, C.POINTER(C.c_void_p)]),
     "nori_gpu_render": (C.c_int, [C.c_void_p, C.POINTER(RenderDesc), C.c_void_p, C.POINTER(Stats)]),
@@ -237,7 +240,8 @@ SIGNATURES = {
 
 # entry points added without an ABI bump (no existing signature or struct changed)
 ADDED_IN_7 = {"nori_gpu_query", "nori_scene_surface", "nori_gpu_camera_rays", "nori_gpu_update_vertices",
-              "nori_gpu_bvh_read", "nori_scene_bvh_refit", "nori_scene_bvh_rebuild", "nori_gpu_rebuild_bvh"}
+              "nori_gpu_bvh_read", "nori_scene_bvh_refit", "nori_scene_bvh_rebuild", "nori_gpu_rebuild_bvh",
+              "nori_scene_shade_rtc", "nori_gpu_shade_rtc_info"}
 
 COMM_ID_BYTES = 128
 SHARD_PASSES, SHARD_BLOCKS = 0, 1
