@@ -1,0 +1,148 @@
+"""The direct_ems / direct_mats / direct_mis integrators written in torch on the query API.
+
+    python examples/direct_torch.py scenes/pa3/odyssey/odyssey_mis.xml out.png --spp 8 --integrator mis
+
+Everything the built-in integrators do at a camera sample is done here from public calls, on
+torch tensors that never leave the GPU -- the first host copy is the finished image:
+
+  1. GpuRenderer.camera_rays      the renderer's own primary rays
+  2. GpuRenderer.sample_uniforms  the renderer's own random numbers (draws 4.. of each sample)
+  3. GpuRenderer.query            closest hits with the full record / any hit for shadow rays
+  4. GpuRenderer.emitter_eval     emission of a hit seen from a point, and its sampling density
+  5. GpuRenderer.emitter_sample   a light sample from a point (direction, maxt, Li / pdf, pdf)
+  6. GpuRenderer.bsdf_eval        f, pdf and the cosine at a hit record
+  7. GpuRenderer.bsdf_sample      a sampled direction with its weight and pdf
+
+The operations follow OneBounce::Li (csrc/onebounce.h) in its order, so each sample's radiance is
+the built-in integrator's, bit for bit.  The image is the per-pixel mean of the samples, i.e. a box
+reconstruction: the library's film weighs the samples with the scene's reconstruction filter, so
+its image is a smoother version of this one.
+
+The library runs on its own stream and its calls block, so the only synchronisation needed is
+torch.cuda.synchronize() before a call that reads what torch has just written.
+"""
+import argparse
+import os
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "nori-ray-tracer_amd"))
+import nori_amd  # noqa: E402
+
+EPS = 1e-4  # NORI_EPSILON
+
+
+def _div(a, b):
+    """a / b rounded once to float32: the quotient of two floats taken in float64 and rounded is
+    the correctly rounded float32 quotient (53 >= 2 * 24 + 2 bits), whatever torch's float32
+    division does."""
+    return (a.double() / b.double()).float()
+
+
+def sample_radiance(r, integrator, k, seed=0):
+    """(H * W, 3) float32 cuda tensor: Li of pass k's sample of every pixel."""
+    scene = r.scene
+    n = scene.height * scene.width
+    dev = torch.device("cuda", r.device)
+    ems, mats, mis = integrator in ("ems", "mis"), integrator in ("mats", "mis"), integrator == "mis"
+    n_em = len(scene.emitters())
+    has_emitter = torch.tensor([sh.emitter >= 0 for sh in scene.shapes()] + [False], device=dev)
+    ndraw = (2 * n_em if ems else 0) + (2 if mats else 0)
+
+    def buf(cols, fill=0.0):
+        return torch.full((n, cols), fill, dtype=torch.float32, device=dev)
+
+    rays, surf, U = buf(8), buf(16), buf(ndraw)
+    torch.cuda.synchronize(dev)
+    r.camera_rays(passes=1, pass_begin=k, seed=seed, out=rays.data_ptr())
+    r.sample_uniforms(4, ndraw, passes=1, pass_begin=k, seed=seed, out=U)
+    r.query(rays.data_ptr(), n=n, surf_out=surf.data_ptr())
+    shape = surf[:, 11].view(torch.int32)
+    hit = shape >= 0
+    o = rays[:, 0:3].contiguous()
+    view = (-rays[:, 4:7]).contiguous()
+    p = surf[:, 0:3].contiguous()
+
+    def shadow_rays(d, maxt):
+        s = buf(8)
+        s[:, 0:3], s[:, 3], s[:, 4:7], s[:, 7] = p, EPS, d, maxt
+        return s
+
+    ee, es, be, bs, hits = buf(4), buf(12), buf(8), buf(8), buf(4)
+    torch.cuda.synchronize(dev)
+    r.emitter_eval(surf, o, n=n, out=ee)  # a miss record gives zeros
+    color = ee[:, 0:3].clone()
+    col = 0
+    if ems:
+        for i in range(n_em):
+            s2 = U[:, col:col + 2].contiguous()
+            col += 2
+            torch.cuda.synchronize(dev)
+            r.emitter_sample(p, s2, emitter=i, n=n, out=es)
+            wi, maxt, Li, pdf_em = es[:, 0:3].contiguous(), es[:, 3], es[:, 4:7], es[:, 7]
+            sh = shadow_rays(wi, torch.where(hit, maxt, torch.full_like(maxt, -1.0)))  # maxt < mint: no hit
+            torch.cuda.synchronize(dev)
+            r.query(sh.data_ptr(), n=n, any_hit=True, hits_out=hits.data_ptr())
+            r.bsdf_eval(surf, view, wi, n=n, out=be)
+            free = hits[:, 1].view(torch.int32) < 0
+            f, pdf_mat, cos = be[:, 0:3], be[:, 3], be[:, 4]
+            if mis:
+                s = pdf_mat + pdf_em
+                w_em = torch.where(s > 0, _div(pdf_em, s), pdf_em)
+                term = ((f * w_em[:, None]) * Li) * cos[:, None]
+            else:
+                term = (f * cos[:, None]) * Li
+            color = torch.where(free[:, None], color + term, color)
+    if mats:
+        s2 = U[:, col:col + 2].contiguous()
+        torch.cuda.synchronize(dev)
+        r.bsdf_sample(surf, view, s2, n=n, out=bs)
+        d2, pdf_mat, w = bs[:, 0:3].contiguous(), bs[:, 3], bs[:, 4:7]
+        go = hit & ~(w == 0).all(1)  # a zero weight ends the sample (no ray)
+        nxt = shadow_rays(d2, float("inf"))
+        nxt[:, 7] = torch.where(go, nxt[:, 7], torch.full_like(nxt[:, 7], -1.0))  # maxt < mint: no hit
+        nh = buf(16)
+        torch.cuda.synchronize(dev)
+        r.query(nxt.data_ptr(), n=n, surf_out=nh.data_ptr())
+        r.emitter_eval(nh, p, n=n, out=ee)
+        Le, pdf_em = ee[:, 0:3], ee[:, 3]
+        lit = go & has_emitter[nh[:, 11].view(torch.int32).long()]  # (-1, a miss, indexes the trailing False)
+        if mis:
+            s = pdf_mat + pdf_em
+            w_mat = torch.where(s > 0, _div(pdf_mat, s), torch.zeros_like(s))
+            add = (w * w_mat[:, None]) * Le
+        else:
+            add = w * Le
+        color = torch.where(lit[:, None], color + add, color)
+    return torch.where(hit[:, None], color, torch.zeros_like(color))
+
+
+def direct_image(r, integrator="mis", spp=1, seed=0):
+    """(H, W, 3) float32 cuda tensor: the mean over passes 0 .. spp-1 of each pixel's samples, added in pass order."""
+    scene = r.scene
+    total = torch.zeros((scene.height * scene.width, 3), dtype=torch.float32, device=torch.device("cuda", r.device))
+    for k in range(spp):
+        total = total + sample_radiance(r, integrator, k, seed)
+    return (total / spp).reshape(scene.height, scene.width, 3)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("scene")
+    ap.add_argument("output", help="PNG file")
+    ap.add_argument("--spp", type=int, default=4)
+    ap.add_argument("--integrator", choices=["ems", "mats", "mis"], default="mis")
+    ap.add_argument("--width", type=int, default=0)
+    ap.add_argument("--height", type=int, default=0)
+    ap.add_argument("--device", type=int, default=0)
+    a = ap.parse_args()
+    scene = nori_amd.load_scene(a.scene, a.width, a.height, 1)
+    with nori_amd.GpuRenderer(scene, a.device) as r:
+        img = direct_image(r, a.integrator, a.spp).cpu().numpy()  # the first host copy
+    nori_amd.write_png(a.output, img)
+    print(f"{a.output}: {scene.width}x{scene.height}, direct_{a.integrator}, {a.spp} spp, mean {img.mean():.4f}")
+
+
+if __name__ == "__main__":
+    main()

@@ -624,6 +624,143 @@ int nori_gpu_query(nori_gpu_ctx *ctx, const nori_gpu_query_desc *desc, const flo
  * Blocking, on the context's stream. */
 int nori_gpu_camera_rays(nori_gpu_ctx *ctx, const nori_gpu_render_desc *desc, float *rays);
 
+/* ---- shading queries: the renderer's BSDFs, emitters and random numbers ----
+ * (no reference counterpart: its BSDFs and emitters are virtuals called from
+ * Li; deviation D16).  With nori_gpu_camera_rays and nori_gpu_query
+ * they are what an integrator written outside the library needs to reproduce
+ * the built-in ones sample for sample.  They trace nothing, so they work on a
+ * context of any integrator and traversal mode, and after
+ * nori_gpu_update_vertices / nori_gpu_rebuild_bvh they answer for the geometry
+ * as it is now (the lights' area tables included).  Blocking, on the context's
+ * stream, like nori_gpu_query. */
+typedef struct nori_gpu_shading_desc {
+    uint32_t n;          /* elements */
+    int32_t  on_device;  /* every array is device memory on the context's device */
+    int32_t  emitter;    /* nori_gpu_emitter_sample only: the emitter for every element when ids == NULL */
+    uint32_t reserved;   /* must be 0 */
+} nori_gpu_shading_desc;
+/* Common to the four calls below.
+ * Arrays.  surf: n records as nori_gpu_query writes them (64 bytes each; 16-byte
+ * aligned on the device).  Directions and points (wi, wo, x, from): n x 3
+ * floats, packed, world space; u: n x 2 floats; ids: n int32 -- each 4-byte
+ * aligned on the device.  out: n rows of 8, 8, 12 and 4 floats, 16-byte aligned
+ * on the device.  on_device: used in place, nothing copied and nothing
+ * allocated per call, the caller has made the inputs ready.  Otherwise host
+ * arrays, staged through context-owned buffers in chunks of at most
+ * NORI_QUERY_CHUNK elements.
+ * Of a record only ns, shape and uv are read (nori_gpu_emitter_eval: p, ns and
+ * shape).  Its shading frame is Frame(ns) (frame.h:49-51, coordinateSystem
+ * common.cpp:274-283): n = ns as stored (not renormalised); if |n.x| > |n.y|
+ * t = (n.z, 0, -n.x) / sqrt(n.x n.x + n.z n.z), else t = (0, n.z, -n.y) /
+ * sqrt(n.y n.y + n.z n.z), the division done as a multiplication by the
+ * correctly rounded reciprocal; s = cross(t, n).  That is the render's own
+ * frame at that hit bit for bit (spheres, meshes with and without normals,
+ * normal-mapped meshes).  to_local(v) = (dot(v, s), dot(v, t), dot(v, n)) with
+ * dot(a, b) = (a.x b.x + a.y b.y) + a.z b.z; to_world(v) = (s v.x + t v.y) + n v.z.
+ * The BSDF is that of shape `shape`, textures are looked up at the record's uv;
+ * for an image texture a uv coordinate that is NaN or beyond +-2^30 / max(W, H)
+ * of the image counts as 0 (so that no texel index can leave its image).
+ * A record whose shape is < 0 or >= the scene's num_shapes is a miss: every
+ * output float of that element is 0 (nori_gpu_query writes shape -1).
+ * NORI_ERR_INVALID, nothing launched: a null ctx, desc or array (ids excepted);
+ * reserved != 0; on_device with a pointer that is misaligned or that the HIP
+ * runtime does not know as device memory; with host arrays a record whose
+ * shape is < -1 or >= num_shapes, or an emitter id (in ids, or desc->emitter
+ * when ids == NULL) outside [0, num_emitters).  With device arrays the
+ * kernels' own range guards apply to records, ids and desc->emitter alike
+ * (zeros, as stated).  n == 0 is a no-op.
+ * Every refusal leaves the context usable. */
+
+/* BSDF::eval and BSDF::pdf at each record.  wi: away from the surface towards
+ * where the path came from (minus the incoming ray's direction); wo: the other
+ * direction.  Both are taken to the shading frame with to_local, the measure
+ * is the solid angle.  out row: eval r, g, b (no cosine factor), pdf,
+ * wo_local.z, wi_local.z, 0, 0 -- the cosines so that a caller forms f * cos
+ * with the renderer's own to_local.  (The `direct` integrator alone calls its
+ * BSDF with the two directions swapped.) */
+int nori_gpu_bsdf_eval(nori_gpu_ctx *ctx, const nori_gpu_shading_desc *desc, const nori_gpu_surface *surf,
+                       const float *wi, const float *wo, float *out);
+/* BSDF::sample at each record with the 2D sample u (x drawn first): the local
+ * wi as above, then out row: to_world(sampled wo) x, y, z; BSDF::pdf of the
+ * sampled pair (what direct_mis and path_mis weigh the BSDF sample with; 0
+ * for the discrete lobes); the sample weight r, g, b (eval * cos / pdf, what
+ * BSDF::sample returns); the measure as a float (1 solid angle, 2 discrete).
+ * A zero weight gives an all-zero row: the renderer ends the path there
+ * without a ray (deviation D1), so there is no direction to report.  The next
+ * ray of the renderer is (p, NORI_EPSILON, direction, +inf). */
+int nori_gpu_bsdf_sample(nori_gpu_ctx *ctx, const nori_gpu_shading_desc *desc, const nori_gpu_surface *surf,
+                         const float *wi, const float *u, float *out);
+/* Emitter::sample of emitter ids[i] (or desc->emitter for every element when
+ * ids is NULL) from the reference point x[i] with the 2D sample u[i].
+ * out row: wi x, y, z (unit, from x towards the light); the shadow ray's maxt;
+ * radiance * attenuation / pdf r, g, b -- NOT scaled by the emitter count;
+ * pdf_em (area light: the area-measure density 1 / area when the sampled
+ * point faces x, else 0, with a zero radiance; point and spot: 1;
+ * environment map: its solid-angle density); the sampled point p x, y, z; 0.
+ * The renderer's shadow ray is (x, NORI_EPSILON, wi, maxt): trace it with
+ * nori_gpu_query(any_hit) and drop the sample if it hits.  The direct_*
+ * integrators sample every emitter in index order with one next2D each; the
+ * path integrators pick one, li = min(floor(N * ul), N - 1) for a draw ul
+ * taken before the 2D sample, and use Li * N (N = num_emitters).
+ * Area lights: mesh -- triangle by the area CDF with sample reuse, then
+ * squareToUniformTriangle, normal interpolated or geometric; sphere --
+ * c + r * squareToUniformSphere(u).  wi = normalize(p - x), attenuation =
+ * dot(n, -wi) / |p - x|^2, maxt = |p - x| - NORI_EPSILON.  Point / spot:
+ * power (times the spot falloff) / (4 pi |p - x|^2).  Environment map: as the
+ * renderer samples it (deviation D4), maxt = 100000; a sample outside [0, 1)
+ * is taken at the nearest table row. */
+int nori_gpu_emitter_sample(nori_gpu_ctx *ctx, const nori_gpu_shading_desc *desc, const int32_t *ids,
+                            const float *x, const float *u, float *out);
+/* What the emitter of the hit shape radiates towards `from`, and the density
+ * with which nori_gpu_emitter_sample would have produced that hit: both at the
+ * record's ns and wi = normalize(p - from) (EmitterQueryRecord(from, p, ns)).
+ * out row: Emitter::eval r, g, b; Emitter::pdf (the pdf_em of
+ * nori_gpu_emitter_sample: bit-equal for the same point and direction).  Area
+ * light: radiance and 1 / area when dot(ns, -wi) > 0, else zeros; environment
+ * map: its value and density along wi.  A shape without an emitter gives zeros.
+ * This is the emission term of every integrator at a hit seen from the ray's
+ * origin, and the emitter side of the BSDF-sampling weight of direct_mis /
+ * path_mis: w_mat = pdf_mat / (pdf_mat + pdf_em) if the sum is > 0. */
+int nori_gpu_emitter_eval(nori_gpu_ctx *ctx, const nori_gpu_shading_desc *desc, const nori_gpu_surface *surf,
+                          const float *from, float *out);
+/* The renderer's own random numbers, the companion of nori_gpu_camera_rays:
+ * draws [first, first + count) of Sampler::next1D on the stream of sample
+ * (pass pass_begin + k, pixel pix = y W + x), wave_seed(seed, (pass_begin + k)
+ * W H + pix), written at out[count (k H W + pix) + j], j < count, for
+ * k < pass_count and the pixels of the selected blocks (other entries are left
+ * untouched).  out: pass_count x H x W x count floats (4-byte aligned on the
+ * device).  A sample consumes its stream in this order: draws 0, 1 the pixel
+ * jitter (x, y); 2, 3 the aperture sample -- drawn for every camera, used or
+ * not; from draw 4 on the integrator's, in the order of its Li.  next2D is two
+ * consecutive draws, x first.  direct_ems / direct_mis: one next2D per emitter
+ * in index order, then (direct_mats, direct_mis) one next2D for the BSDF
+ * sample.  Li of those integrators for a camera ray (o, d), every operation a
+ * single float operation in the order written (a miss: 0):
+ *   L = Emitter::eval at the hit seen from o        (nori_gpu_emitter_eval)
+ *   per emitter i (direct_ems, direct_mis), with s = its next2D:
+ *     (wi, maxt, Li, pdf_em) = nori_gpu_emitter_sample(p, s); skip if the
+ *     shadow ray hits; (f, pdf_mat, cos) = nori_gpu_bsdf_eval(-d, wi);
+ *     direct_ems: L = L + (f * cos) * Li
+ *     direct_mis: w = pdf_mat + pdf_em > 0 ? pdf_em / (pdf_mat + pdf_em) : pdf_em;
+ *                 L = L + ((f * w) * Li) * cos
+ *   then (direct_mats, direct_mis), with s = the last next2D:
+ *     (dir, pdf_mat, weight) = nori_gpu_bsdf_sample(-d, s); a zero weight ends
+ *     it; the ray (p, NORI_EPSILON, dir, +inf) must hit a shape with an
+ *     emitter, else it ends; (Le, pdf_em) = nori_gpu_emitter_eval there seen from p;
+ *     direct_mats: L = L + weight * Le
+ *     direct_mis:  w = pdf_mat + pdf_em > 0 ? pdf_mat / (pdf_mat + pdf_em) : 0;
+ *                  L = L + (weight * w) * Le
+ * (tests/shading_compose.py is this text in numpy; the per-pixel statistics of
+ * a one-pass nori_gpu_render hold 0 + L of each sample.)
+ * From `desc`: pass_begin, pass_count (0 = the scene's sampleCount),
+ * seed, num_blocks / block_ids and output_on_device; the other fields are
+ * ignored, variance_out must be NULL.  NORI_ERR_INVALID: a null argument,
+ * count == 0, first + count overflowing 32 bits, variance_out set, a device
+ * pointer that is misaligned or not device memory.  Blocking, on the context's
+ * stream. */
+int nori_gpu_sample_uniforms(nori_gpu_ctx *ctx, const nori_gpu_render_desc *desc, uint32_t first,
+                             uint32_t count, float *out);
+
 /* ---- dynamic geometry: new vertex positions, the BVH refitted on the device ----
  * (no reference counterpart: the reference builds its BVH once, in
  * Scene::activate; deviation D14) */

@@ -2,8 +2,9 @@
 // defined beside its kernel: launch_shade in kernels_shade.hip; launch_mark,
 // launch_tail_prefix and launch_finish in kernels_finish.hip; launch_features
 // in kernels_features.hip; launch_surface and launch_camera_rays in
-// kernels_query.hip; the denoisers, the block error and the refit in
-// denoise.hip, block_error.hip and refit.hip; all others in kernels.hip.
+// kernels_query.hip; the shading queries in kernels_shading.hip; the
+// denoisers, the block error and the refit in denoise.hip, block_error.hip
+// and refit.hip; all others in kernels.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -166,6 +167,27 @@ hipError_t launch_surface(const DevScene &S, const float4 *rays, const float4 *h
 // `pixels` (y*W + x), written at rays[8 * (k * W * H + pix)]; np * M < 2^31.
 hipError_t launch_camera_rays(const DevScene &S, const uint32_t *pixels, uint32_t M, uint32_t pass_begin, uint32_t k0,
                               uint32_t np, uint64_t seed, float *rays, hipStream_t st);
+// Shading queries (kernels_shading.hip; stated at nori_gpu_bsdf_eval ..
+// nori_gpu_sample_uniforms in nori_gpu.h): element i < n of each array, all
+// device memory.  surf: 64-byte records (four float4, 16-byte aligned);
+// wi / wo / x / from: 3 floats and u: 2 floats per element (4-byte aligned);
+// out: 2, 2, 3 and 1 float4 per element.  A record whose shape is not below
+// num_shapes and an emitter id not below S.num_emitters give zeros.
+hipError_t launch_bsdf_eval(const DevScene &S, uint32_t num_shapes, const float4 *surf, const float *wi,
+                            const float *wo, uint32_t n, float4 *out, hipStream_t st);
+hipError_t launch_bsdf_sample(const DevScene &S, uint32_t num_shapes, const float4 *surf, const float *wi,
+                              const float *u, uint32_t n, float4 *out, hipStream_t st);
+// ids == null: `emitter` for every element
+hipError_t launch_emitter_sample(const DevScene &S, const int32_t *ids, int32_t emitter, const float *x, const float *u,
+                                 uint32_t n, float4 *out, hipStream_t st);
+hipError_t launch_emitter_eval(const DevScene &S, uint32_t num_shapes, const float4 *surf, const float *from,
+                               uint32_t n, float4 *out, hipStream_t st);
+// Draws [first, first + count) of the stream of sample (pass pass_begin + k,
+// pixel pix) for k in [k0, k0 + np) and the M entries of `pixels`, written at
+// out[count * (k * W * H + pix)]; np * M < 2^31.
+hipError_t launch_sample_uniforms(const DevScene &S, const uint32_t *pixels, uint32_t M, uint32_t pass_begin,
+                                  uint32_t k0, uint32_t np, uint64_t seed, uint32_t first, uint32_t count, float *out,
+                                  hipStream_t st);
 hipError_t launch_splat(const DevScene &S, const float4 *rec, const SplatDesc &sd, uint32_t nblocks, float *film,
                         Counters *C, hipStream_t st);
 // The adaptive sampler's block error (block_error.hip; the metric is stated

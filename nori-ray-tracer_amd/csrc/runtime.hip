@@ -239,6 +239,8 @@ struct nori_gpu_ctx {
     // serves a device query without a hit output), reused across calls; events around the two kernels
     DevBuf q_rays, q_hits, q_surf;
     hipEvent_t q_ev[3] = {};
+    // the shading queries (nori_gpu_bsdf_eval ..): staging of up to three host input arrays and the output
+    DevBuf sh_in[3], sh_out;
     DevBuf ph, ph_rgbe, ph_tab, ph_start;             // photonmapper: photon map (photon_map.cpp) and its hash-grid buckets
     // nori_gpu_update_vertices: the refit schedule (host copy of its level bounds, device copy of
     // its slots), staging of host positions / normals, the non-finite counter, the shapes as
@@ -1945,6 +1947,105 @@ int camera_rays(nori_gpu_ctx &c, const nori_gpu_render_desc &rd, float *rays) {
     return NORI_OK;
 }
 
+// The shading queries (nori_gpu_bsdf_eval .. nori_gpu_emitter_eval, stated in
+// nori_gpu.h): one element-wise kernel over up to three input arrays and one
+// output array.  Device arrays are checked (alignment, and that the runtime
+// knows them as device memory: update_vertices' check) and used in place;
+// host arrays pass through the context's sh_in / sh_out buffers in chunks of
+// at most NORI_QUERY_CHUNK elements.
+struct ShadeArr {
+    const void *p;   // may be null only where the call allows it (ids)
+    size_t stride;   // bytes per element
+    size_t align;    // of a device pointer
+};
+template <class Launch>
+int shading_call(nori_gpu_ctx &c, const char *name, const nori_gpu_shading_desc &sd, const ShadeArr (&in)[3], void *out,
+                 size_t out_stride, Launch &&launch) {
+    HIP_TRY(hipSetDevice(c.device));
+    const uint32_t n = sd.n;
+    if (sd.on_device) {
+        const ShadeArr all[4] = {in[0], in[1], in[2], ShadeArr{out, out_stride, 16}};
+        for (const ShadeArr &a : all) {
+            if (!a.p) continue;
+            if ((uintptr_t)a.p % a.align)
+                throw NoriException(NORI_ERR_INVALID, std::string(name) + ": a device pointer is not " +
+                                                          std::to_string(a.align) + "-byte aligned");
+            hipPointerAttribute_t at{};
+            if (hipPointerGetAttributes(&at, a.p) != hipSuccess ||
+                (at.type != hipMemoryTypeDevice && at.type != hipMemoryTypeManaged)) {
+                (void)hipGetLastError();
+                throw NoriException(NORI_ERR_INVALID, std::string(name) + ": on_device with a pointer that is not device memory");
+            }
+        }
+        const void *d[3] = {in[0].p, in[1].p, in[2].p};
+        HIP_TRY(launch(d, out, n));
+        HIP_TRY(hipStreamSynchronize(c.stream));
+        return NORI_OK;
+    }
+    const uint32_t chunk = std::min(n, query_chunk());
+    for (int k = 0; k < 3; ++k)
+        if (in[k].p) c.sh_in[k].ensure(in[k].stride * (size_t)chunk);
+    c.sh_out.ensure(out_stride * (size_t)chunk);
+    for (uint64_t i0 = 0; i0 < n; i0 += chunk) {
+        const uint32_t m = (uint32_t)std::min<uint64_t>(chunk, n - i0);
+        const void *d[3] = {nullptr, nullptr, nullptr};
+        for (int k = 0; k < 3; ++k) {
+            if (!in[k].p) continue;
+            HIP_TRY(hipMemcpyAsync(c.sh_in[k].p, (const char *)in[k].p + in[k].stride * i0, in[k].stride * (size_t)m,
+                                   hipMemcpyHostToDevice, c.stream));
+            d[k] = c.sh_in[k].p;
+        }
+        HIP_TRY(launch(d, c.sh_out.p, m));
+        HIP_TRY(hipMemcpyAsync((char *)out + out_stride * i0, c.sh_out.p, out_stride * (size_t)m, hipMemcpyDeviceToHost,
+                               c.stream));
+        HIP_TRY(hipStreamSynchronize(c.stream));
+    }
+    return NORI_OK;
+}
+// Host records: the shape index must be the miss's -1 or a shape of the scene.
+void check_host_records(const nori_gpu_ctx &c, const char *name, const nori_gpu_surface *surf, uint32_t n) {
+    const int32_t ns = (int32_t)c.hshapes.size();
+    for (uint32_t i = 0; i < n; ++i)
+        if (surf[i].shape < -1 || surf[i].shape >= ns)
+            throw NoriException(NORI_ERR_INVALID, std::string(name) + ": record " + std::to_string(i) + " names shape " +
+                                                      std::to_string(surf[i].shape) + " of " + std::to_string(ns));
+}
+
+// nori_gpu_sample_uniforms: k_sample_uniforms over the selected blocks'
+// pixels, in chunks of passes like camera_rays (and with its handling of a
+// host buffer: uploaded first, so that unselected entries keep their values).
+int sample_uniforms(nori_gpu_ctx &c, const nori_gpu_render_desc &rd, uint32_t first, uint32_t count, float *out) {
+    HIP_TRY(hipSetDevice(c.device));
+    if (rd.variance_out) throw NoriException(NORI_ERR_INVALID, "nori_gpu_sample_uniforms: variance_out must be NULL");
+    if (count == 0 || first + count < first)
+        throw NoriException(NORI_ERR_INVALID, "nori_gpu_sample_uniforms: count is 0 or first + count overflows");
+    work_lists(c, rd);
+    const uint32_t M = (uint32_t)c.hpixels.size(), passes = rd.pass_count ? rd.pass_count : c.spp;
+    if (passes == 0 || M == 0) throw NoriException(NORI_ERR_INVALID, "nothing to do (pass_count or blocks empty)");
+    const size_t bytes = 4 * (size_t)count * (size_t)passes * (size_t)c.S.W * (size_t)c.S.H;
+    float *dev = out;
+    if (rd.output_on_device) {
+        if ((uintptr_t)out % 4) throw NoriException(NORI_ERR_INVALID, "nori_gpu_sample_uniforms: the device buffer must be 4-byte aligned");
+        hipPointerAttribute_t at{};
+        if (hipPointerGetAttributes(&at, out) != hipSuccess ||
+            (at.type != hipMemoryTypeDevice && at.type != hipMemoryTypeManaged)) {
+            (void)hipGetLastError();
+            throw NoriException(NORI_ERR_INVALID, "nori_gpu_sample_uniforms: output_on_device with a pointer that is not device memory");
+        }
+    } else {
+        c.sh_out.ensure(bytes);
+        dev = c.sh_out.as<float>();
+        HIP_TRY(hipMemcpyAsync(dev, out, bytes, hipMemcpyHostToDevice, c.stream));
+    }
+    const uint32_t chunk = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(passes, ((uint64_t)1 << 24) / M));
+    for (uint32_t k0 = 0; k0 < passes; k0 += chunk)
+        HIP_TRY(launch_sample_uniforms(c.S, c.pixels.as<uint32_t>(), M, rd.pass_begin, k0, std::min(chunk, passes - k0),
+                                       rd.seed, first, count, dev, c.stream));
+    if (!rd.output_on_device) HIP_TRY(hipMemcpyAsync(out, dev, bytes, hipMemcpyDeviceToHost, c.stream));
+    HIP_TRY(hipStreamSynchronize(c.stream));
+    return NORI_OK;
+}
+
 // nori_gpu_update_vertices (stated in nori_gpu.h): validate, then on the
 // context's stream count the non-finite inputs (nothing is modified before
 // that count is back), set the vertices, rebuild the records, refit the boxes
@@ -2824,6 +2925,87 @@ int nori_gpu_camera_rays(nori_gpu_ctx *c, const nori_gpu_render_desc *rd, float 
         if (!c || !rd || !rays) return fail(NORI_ERR_INVALID, "null argument");
         if (rd->num_blocks && !rd->block_ids) return fail(NORI_ERR_INVALID, "block_ids is null");
         return camera_rays(*c, *rd, rays);
+    });
+}
+
+int nori_gpu_bsdf_eval(nori_gpu_ctx *c, const nori_gpu_shading_desc *sd, const nori_gpu_surface *surf, const float *wi,
+                       const float *wo, float *out) {
+    return guarded([&] {
+        if (!c || !sd || !surf || !wi || !wo || !out) return fail(NORI_ERR_INVALID, "null argument");
+        if (sd->reserved != 0) return fail(NORI_ERR_INVALID, "nori_gpu_bsdf_eval: reserved must be 0");
+        if (sd->n == 0) return NORI_OK;
+        if (!sd->on_device) check_host_records(*c, "nori_gpu_bsdf_eval", surf, sd->n);
+        const uint32_t shapes = (uint32_t)c->hshapes.size();
+        return shading_call(*c, "nori_gpu_bsdf_eval", *sd, {{surf, 64, 16}, {wi, 12, 4}, {wo, 12, 4}}, out, 32,
+                            [&](const void *const *d, void *o, uint32_t m) {
+                                return launch_bsdf_eval(c->S, shapes, (const float4 *)d[0], (const float *)d[1],
+                                                        (const float *)d[2], m, (float4 *)o, c->stream);
+                            });
+    });
+}
+
+int nori_gpu_bsdf_sample(nori_gpu_ctx *c, const nori_gpu_shading_desc *sd, const nori_gpu_surface *surf, const float *wi,
+                         const float *u, float *out) {
+    return guarded([&] {
+        if (!c || !sd || !surf || !wi || !u || !out) return fail(NORI_ERR_INVALID, "null argument");
+        if (sd->reserved != 0) return fail(NORI_ERR_INVALID, "nori_gpu_bsdf_sample: reserved must be 0");
+        if (sd->n == 0) return NORI_OK;
+        if (!sd->on_device) check_host_records(*c, "nori_gpu_bsdf_sample", surf, sd->n);
+        const uint32_t shapes = (uint32_t)c->hshapes.size();
+        return shading_call(*c, "nori_gpu_bsdf_sample", *sd, {{surf, 64, 16}, {wi, 12, 4}, {u, 8, 4}}, out, 32,
+                            [&](const void *const *d, void *o, uint32_t m) {
+                                return launch_bsdf_sample(c->S, shapes, (const float4 *)d[0], (const float *)d[1],
+                                                          (const float *)d[2], m, (float4 *)o, c->stream);
+                            });
+    });
+}
+
+int nori_gpu_emitter_sample(nori_gpu_ctx *c, const nori_gpu_shading_desc *sd, const int32_t *ids, const float *x,
+                            const float *u, float *out) {
+    return guarded([&] {
+        if (!c || !sd || !x || !u || !out) return fail(NORI_ERR_INVALID, "null argument");
+        if (sd->reserved != 0) return fail(NORI_ERR_INVALID, "nori_gpu_emitter_sample: reserved must be 0");
+        if (sd->n == 0) return NORI_OK;
+        const int32_t ne = (int32_t)c->S.num_emitters;
+        // host arrays: the host can look at every id (device arrays: the kernel's guard gives zeros)
+        if (!sd->on_device && !ids && (sd->emitter < 0 || sd->emitter >= ne))
+            return fail(NORI_ERR_INVALID, "nori_gpu_emitter_sample: desc->emitter " + std::to_string(sd->emitter) +
+                                              " is outside the scene's " + std::to_string(ne) + " emitters");
+        if (!sd->on_device && ids)
+            for (uint32_t i = 0; i < sd->n; ++i)
+                if (ids[i] < 0 || ids[i] >= ne)
+                    return fail(NORI_ERR_INVALID, "nori_gpu_emitter_sample: ids[" + std::to_string(i) + "] = " +
+                                                      std::to_string(ids[i]) + " is outside the scene's " +
+                                                      std::to_string(ne) + " emitters");
+        return shading_call(*c, "nori_gpu_emitter_sample", *sd, {{ids, 4, 4}, {x, 12, 4}, {u, 8, 4}}, out, 48,
+                            [&](const void *const *d, void *o, uint32_t m) {
+                                return launch_emitter_sample(c->S, (const int32_t *)d[0], sd->emitter, (const float *)d[1],
+                                                             (const float *)d[2], m, (float4 *)o, c->stream);
+                            });
+    });
+}
+
+int nori_gpu_emitter_eval(nori_gpu_ctx *c, const nori_gpu_shading_desc *sd, const nori_gpu_surface *surf,
+                          const float *from, float *out) {
+    return guarded([&] {
+        if (!c || !sd || !surf || !from || !out) return fail(NORI_ERR_INVALID, "null argument");
+        if (sd->reserved != 0) return fail(NORI_ERR_INVALID, "nori_gpu_emitter_eval: reserved must be 0");
+        if (sd->n == 0) return NORI_OK;
+        if (!sd->on_device) check_host_records(*c, "nori_gpu_emitter_eval", surf, sd->n);
+        const uint32_t shapes = (uint32_t)c->hshapes.size();
+        return shading_call(*c, "nori_gpu_emitter_eval", *sd, {{surf, 64, 16}, {from, 12, 4}, {nullptr, 0, 4}}, out, 16,
+                            [&](const void *const *d, void *o, uint32_t m) {
+                                return launch_emitter_eval(c->S, shapes, (const float4 *)d[0], (const float *)d[1], m,
+                                                           (float4 *)o, c->stream);
+                            });
+    });
+}
+
+int nori_gpu_sample_uniforms(nori_gpu_ctx *c, const nori_gpu_render_desc *rd, uint32_t first, uint32_t count, float *out) {
+    return guarded([&] {
+        if (!c || !rd || !out) return fail(NORI_ERR_INVALID, "null argument");
+        if (rd->num_blocks && !rd->block_ids) return fail(NORI_ERR_INVALID, "block_ids is null");
+        return sample_uniforms(*c, *rd, first, count, out);
     });
 }
 

@@ -127,10 +127,14 @@ ND void env_sample1D(const float *pf, const float *P, int cols, float s, float &
 }
 // EnvironmentMap::sample (envmap.cpp:158-181); deviation D4: the Jacobian
 // uses the sampled direction (the reference reads lRec.wi uninitialised).
+// CLAMP (the shading queries, whose samples are the caller's): the sampled
+// row is kept inside the tables for any smp -- row = (int)u for every u in
+// [0, R - 1], so nothing else changes; the renderers instantiate CLAMP = false.
+template <bool CLAMP = false>
 ND V3 env_sample(const DevScene &S, const DevEmitter &e, V2 smp, V3 &wi) {
     float u, v, u_pdf, v_pdf;
     env_sample1D(S.env + e.pmarg_off, S.env + e.cmarg_off, e.R, smp.x, u, u_pdf);
-    const int row = (int)u;
+    const int row = CLAMP ? (int)(u >= 0.0f ? smin(u, (float)(e.R - 1)) : 0.0f) : (int)u;  // (CLAMP: NaN -> row 0)
     env_sample1D(S.env + e.pdf_off + (size_t)row * e.C, S.env + e.cdf_off + (size_t)row * (e.C + 1), e.C, smp.y, v,
                  v_pdf);
     const float theta = (float)((double)u * M_PI / (double)(e.R - 1));  // invMapIntersect
@@ -398,7 +402,7 @@ struct NeeSample {
 // Emitter::sample of one emitter from x with the 2D sample s2: radiance over
 // pdf (not yet scaled by the emitter count), direction, area-measure pdf and
 // the shadow ray's maxt.
-template <bool FULL = true>
+template <bool FULL = true, bool CLAMP = false>
 ND NeeSample emitter_sample_one(const DevScene &S, const DevEmitter &E, V3 x, V2 s2) {
     NeeSample r;
     if (FULL && (E.type == NORI_EMITTER_POINT || E.type == NORI_EMITTER_SPOT)) {
@@ -408,7 +412,7 @@ ND NeeSample emitter_sample_one(const DevScene &S, const DevEmitter &E, V3 x, V2
         return r;
     }
     if (FULL && E.type == NORI_EMITTER_ENVMAP) {
-        r.Li = env_sample(S, E, s2, r.wi);
+        r.Li = env_sample<CLAMP>(S, E, s2, r.wi);
         r.pdf_em = env_pdf(S, E, r.wi);
         r.maxt = kEnvTFar;               // shadow ray (ref, wi, Epsilon, T_FAR)
         r.p = x + r.wi * kEnvTFar;       // D4: lRec.p is never set by the reference

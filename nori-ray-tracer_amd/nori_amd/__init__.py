@@ -643,6 +643,105 @@ class GpuRenderer:
         check(lib().nori_gpu_camera_rays(self._h, C.byref(rd), C.c_void_p(out.ctypes.data)))
         return out
 
+    def _shading(self, fn, name, arrays, cols, n, out, emitter=0):
+        """One shading query.  arrays: [(argument, dtype or None for records, columns, optional)];
+        all numpy (host form, the result is returned) or all device addresses with n= and out=."""
+        sd = _abi.ShadingDesc(0, 0, int(emitter), 0)
+        given = [a for a, _, _, opt in arrays if not (opt and a is None)]
+        host = [isinstance(a, np.ndarray) for a in given]
+        if any(host) != all(host):
+            raise ValueError(f"{name}: the arrays must all be numpy arrays or all be device addresses")
+        if not all(host):
+            if n is None or out is None or isinstance(out, np.ndarray):
+                raise ValueError(f"{name}: device addresses need n= and a device address out=")
+            sd.n, sd.on_device = int(n), 1
+            ptrs = [None if a is None else C.c_void_p(int(a.data_ptr() if hasattr(a, "data_ptr") else a))
+                    for a, _, _, _ in arrays]
+            check(fn(self._h, C.byref(sd), *ptrs, C.c_void_p(int(out.data_ptr() if hasattr(out, "data_ptr") else out))))
+            return None
+        conv = []
+        for a, dt, k, opt in arrays:
+            if a is None:
+                conv.append(None)
+                continue
+            if dt is None:  # hit records
+                a = np.ascontiguousarray(a, dtype=SURFACE_DTYPE).reshape(-1)
+            else:
+                a = np.ascontiguousarray(a, dtype=dt)
+                a = a.reshape(-1) if k == 1 else a
+                if k > 1 and (a.ndim != 2 or a.shape[1] != k):
+                    raise ValueError(f"{name}: an array of shape {a.shape}, expected (n, {k})")
+            conv.append(a)
+        sizes = {a.shape[0] for a in conv if a is not None}
+        if len(sizes) != 1:
+            raise ValueError(f"{name}: the arrays have different lengths {sorted(sizes)}")
+        sd.n = sizes.pop()
+        if out is None:
+            out = np.zeros((sd.n, cols), np.float32)
+        assert isinstance(out, np.ndarray) and out.dtype == np.float32 and out.flags.c_contiguous and out.shape == (sd.n, cols)
+        ptrs = [None if a is None else C.c_void_p(a.ctypes.data) for a in conv]
+        check(fn(self._h, C.byref(sd), *ptrs, C.c_void_p(out.ctypes.data)))
+        return out
+
+    def bsdf_eval(self, surf, wi, wo, n=None, out=None):
+        """BSDF::eval and BSDF::pdf at hit records (nori_gpu_bsdf_eval, stated in nori_gpu.h).
+
+        surf: the "surf" records of query(); wi (towards where the path came from) and wo: (n, 3)
+        world-space directions.  Returns (n, 8) float32: eval rgb (no cosine), pdf, wo_local.z,
+        wi_local.z, 0, 0; a miss record gives zeros.  Device form: every argument an int device
+        address or a torch tensor on the context's device, with n= and out= (n x 8 floats, 16-byte
+        aligned); None is returned and the buffers must be ready before the call."""
+        return self._shading(lib().nori_gpu_bsdf_eval, "bsdf_eval",
+                             [(surf, None, 0, False), (wi, np.float32, 3, False), (wo, np.float32, 3, False)], 8, n, out)
+
+    def bsdf_sample(self, surf, wi, u, n=None, out=None):
+        """BSDF::sample at hit records with the 2D samples u (n, 2) (nori_gpu_bsdf_sample).
+        Returns (n, 8) float32: the sampled world direction, BSDF::pdf of the sampled pair, the
+        weight rgb, the measure (1 solid angle, 2 discrete); a zero weight gives a zero row.
+        Device form as bsdf_eval."""
+        return self._shading(lib().nori_gpu_bsdf_sample, "bsdf_sample",
+                             [(surf, None, 0, False), (wi, np.float32, 3, False), (u, np.float32, 2, False)], 8, n, out)
+
+    def emitter_sample(self, x, u, ids=None, emitter=0, n=None, out=None):
+        """Emitter::sample from the points x (n, 3) with the 2D samples u (n, 2) (nori_gpu_emitter_sample):
+        emitter ids[i] (int32), or `emitter` for every element when ids is None.  Returns (n, 12)
+        float32: wi, the shadow ray's maxt, radiance * attenuation / pdf rgb (not scaled by the emitter
+        count), pdf_em, the sampled point, 0.  The shadow ray is (x, 1e-4, wi, maxt).  Device form as
+        bsdf_eval (out: n x 12 floats)."""
+        return self._shading(lib().nori_gpu_emitter_sample, "emitter_sample",
+                             [(ids, np.int32, 1, True), (x, np.float32, 3, False), (u, np.float32, 2, False)], 12, n, out,
+                             emitter=emitter)
+
+    def emitter_eval(self, surf, origin, n=None, out=None):
+        """What the emitter of each hit shape radiates towards `origin` (n, 3), and the density with
+        which emitter_sample would have produced the hit (nori_gpu_emitter_eval).  Returns (n, 4)
+        float32: Emitter::eval rgb, Emitter::pdf; zeros for a shape without an emitter and for a
+        miss.  Device form as bsdf_eval (out: n x 4 floats)."""
+        return self._shading(lib().nori_gpu_emitter_eval, "emitter_eval",
+                             [(surf, None, 0, False), (origin, np.float32, 3, False)], 4, n, out)
+
+    def sample_uniforms(self, first, count, passes=None, pass_begin=0, blocks=None, seed=0, out=None):
+        """The renderer's own random numbers (nori_gpu_sample_uniforms): draws [first, first+count)
+        of the stream of every sample of passes [pass_begin, pass_begin+passes) of `blocks` (all if
+        None) as (passes, H, W, count) float32.  Draws 0-1 are the pixel jitter, 2-3 the aperture
+        sample, the integrator's start at 4; a 2D sample is two consecutive draws, x first.  Only the
+        selected blocks' pixels are written (into `out` when given).  `out` may be an int device
+        address (or torch tensor) of such a buffer: None is returned then."""
+        rd, ids = self._desc(passes, pass_begin, blocks, seed, 0, False)
+        if rd.pass_count == 0:
+            rd.pass_count = max(1, int(self.scene.spp))
+        shape = (rd.pass_count, self.scene.height, self.scene.width, int(count))
+        if out is not None and not isinstance(out, np.ndarray):
+            rd.output_on_device = 1
+            check(lib().nori_gpu_sample_uniforms(self._h, C.byref(rd), int(first), int(count),
+                                                 C.c_void_p(int(out.data_ptr() if hasattr(out, "data_ptr") else out))))
+            return None
+        if out is None:
+            out = np.zeros(shape, np.float32)
+        assert out.dtype == np.float32 and out.flags.c_contiguous and out.shape == shape
+        check(lib().nori_gpu_sample_uniforms(self._h, C.byref(rd), int(first), int(count), C.c_void_p(out.ctypes.data)))
+        return out
+
     def _vertex_arg(self, a, what):
         """(address, on_device, keep-alive) of a positions / normals argument of update_vertices."""
         n = self.scene.desc.num_vertices

@@ -138,6 +138,11 @@ class QueryDesc(C.Structure):
     _fields_ = [("n", C.c_uint32), ("any_hit", C.c_int32), ("on_device", C.c_int32), ("reserved", C.c_uint32)]
 
 
+class ShadingDesc(C.Structure):
+    """nori_gpu_shading_desc: the common descriptor of the shading queries."""
+    _fields_ = [("n", C.c_uint32), ("on_device", C.c_int32), ("emitter", C.c_int32), ("reserved", C.c_uint32)]
+
+
 class UpdateDesc(C.Structure):
     """nori_gpu_update_desc: new vertex positions (and normals) for nori_gpu_update_vertices."""
     _fields_ = [("positions", C.c_void_p), ("normals", C.c_void_p), ("num_vertices", C.c_uint32),
@@ -214,6 +219,12 @@ SIGNATURES = {
                                  C.POINTER(Stats)]),
     "nori_scene_surface": (C.c_int, [C.POINTER(SceneDesc), C.c_uint32, C.POINTER(C.c_float), C.c_void_p, C.c_void_p]),
     "nori_gpu_camera_rays": (C.c_int, [C.c_void_p, C.POINTER(RenderDesc), C.c_void_p]),
+    "nori_gpu_bsdf_eval": (C.c_int, [C.c_void_p, C.POINTER(ShadingDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nori_gpu_bsdf_sample": (C.c_int, [C.c_void_p, C.POINTER(ShadingDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nori_gpu_emitter_sample": (C.c_int, [C.c_void_p, C.POINTER(ShadingDesc), C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p]),
+    "nori_gpu_emitter_eval": (C.c_int, [C.c_void_p, C.POINTER(ShadingDesc), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nori_gpu_sample_uniforms": (C.c_int, [C.c_void_p, C.POINTER(RenderDesc), C.c_uint32, C.c_uint32, C.c_void_p]),
     "nori_gpu_update_vertices": (C.c_int, [C.c_void_p, C.POINTER(UpdateDesc), C.POINTER(UpdateStats)]),
     "nori_gpu_bvh_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint32)]),
     "nori_scene_bvh_refit": (C.c_int, [C.POINTER(SceneDesc), C.POINTER(C.c_float), C.POINTER(C.c_float),
@@ -241,7 +252,8 @@ SIGNATURES = {
 # entry points added without an ABI bump (no existing signature or struct changed)
 ADDED_IN_7 = {"nori_gpu_query", "nori_scene_surface", "nori_gpu_camera_rays", "nori_gpu_update_vertices",
               "nori_gpu_bvh_read", "nori_scene_bvh_refit", "nori_scene_bvh_rebuild", "nori_gpu_rebuild_bvh",
-              "nori_scene_shade_rtc", "nori_gpu_shade_rtc_info"}
+              "nori_scene_shade_rtc", "nori_gpu_shade_rtc_info", "nori_gpu_bsdf_eval", "nori_gpu_bsdf_sample",
+              "nori_gpu_emitter_sample", "nori_gpu_emitter_eval", "nori_gpu_sample_uniforms"}
 
 COMM_ID_BYTES = 128
 SHARD_PASSES, SHARD_BLOCKS = 0, 1
