@@ -1,5 +1,5 @@
 // comm.h -- internal interface of comm.cpp (RCCL film exchange), used by
-// runtime.hip's nori_gpu_comm_* / nori_gpu_render_sharded entry points.
+// sharded.hip's nori_gpu_comm_* / nori_gpu_render_sharded entry points.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -3,7 +3,7 @@
 // variants) and k_reset; one sample per thread (k_direct, k_photons); the
 // film splat (k_splat).
 //
-// One iteration of the state machine (runtime.hip drives it):
+// One iteration of the state machine (render.hip drives it):
 //   k_shade   : per path: surface hit -> emission, next-event estimation
 //               (light sample + shadow ray), Russian roulette, BSDF sample,
 //               or regeneration of a finished path slot with a new camera

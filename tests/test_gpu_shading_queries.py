@@ -34,7 +34,7 @@ pytestmark = pytest.mark.gpu
 f32, u32 = np.float32, np.uint32
 VEACH = ("pa3", "veach_mi", "veach_mis.xml")
 TEXTURED = ("project", "textured", "cbox_path_mis.xml")
-SCAN_MAX_PRIMS = 64  # runtime.hip kScanMaxPrims: contexts of larger scenes traverse the BVH
+SCAN_MAX_PRIMS = 64  # scene_prep.h kScanMaxPrims: contexts of larger scenes traverse the BVH
 
 
 def local32(ns, v):

@@ -92,7 +92,7 @@ def test_class_reproduces_the_direct_weights(radius, B):
         c = classes(X, J, radius, B)
         assert c.min() >= 0 and c.max() < 4 * lk  # 8 bits, k_splat's table size
         got = class_indices(c, radius, B)
-        # the weight of index R is the table's 0 (runtime.hip filter_table), as
+        # the weight of index R is the table's 0 (scene_prep.cpp filter_table), as
         # outside the box: fl(P + r) and fl(P - r) can round across an integer
         # only at a cell |c - P| >= r, i.e. index R (so the comparison is of weights)
         want, got = np.where(want == R, -1, want), np.where(got == R, -1, got)

@@ -110,7 +110,7 @@ def test_shard_block_lists_are_checked_and_deduplicated(built):
 
 
 def test_status_word_encoding(built):
-    """The status exchange's word (runtime.hip comm_status_word): severity << 16
+    """The status exchange's word (shard.cpp comm_status_word): severity << 16
     | rank, reduced by max -- the worst outcome wins and names its rank."""
     from nori_amd import _abi
     f = _abi.lib().nori_gpu_comm_status_word

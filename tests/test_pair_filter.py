@@ -1,5 +1,5 @@
 """The binned extension kernel's in-plane filter (scan.h pair_candidate,
-constants from runtime.hip plane_filters) is exact: whenever it says a ray
+constants from scene_prep.cpp plane_filters) is exact: whenever it says a ray
 cannot hit an axis-plane pair, the reference's Moller-Trumbore test
 (mesh.cpp:83-120) rejects that ray for both triangles of the pair.  Checked in
 float32 with the device's operation order (numpy float32 rounds like the GPU;

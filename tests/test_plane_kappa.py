@@ -1,6 +1,6 @@
 """The axis-plane proofs (scan.h plane_may_hit, pair_candidate) hold for
 kappa = (|P| + |Q|) / |P - Q| <= 32 of a triangle's normal products, which
-runtime.hip axis_plane checks.  The Cornell box's rectangles have kappa = 1;
+scene_prep.cpp axis_plane checks.  The Cornell box's rectangles have kappa = 1;
 here skewed sliver triangles in y = const planes span kappa 1.5 .. 64: the
 host must class exactly those with kappa <= 32 as plane triangles
 (nori_scene_scan_list), and for every one it accepted, both culls must imply
