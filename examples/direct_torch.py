@@ -1,6 +1,6 @@
 """The direct_ems / direct_mats / direct_mis integrators written in torch on the query API.
 
-    python examples/direct_torch.py scenes/pa3/odyssey/odyssey_mis.xml out.png --spp 8 --integrator mis
+    python examples/direct_torch.py scenes/pa3/odyssey/odyssey_mis.xml out.png --spp 8 --integrator mis [--film]
 
 Everything the built-in integrators do at a camera sample is done here from public calls, on
 torch tensors that never leave the GPU -- the first host copy is the finished image:
@@ -12,11 +12,14 @@ torch tensors that never leave the GPU -- the first host copy is the finished im
   5. GpuRenderer.emitter_sample   a light sample from a point (direction, maxt, Li / pdf, pdf)
   6. GpuRenderer.bsdf_eval        f, pdf and the cosine at a hit record
   7. GpuRenderer.bsdf_sample      a sampled direction with its weight and pdf
+  8. GpuRenderer.film_splat_passes  the samples filtered into the film (--film)
 
 The operations follow OneBounce::Li (csrc/onebounce.h) in its order, so each sample's radiance is
-the built-in integrator's, bit for bit.  The image is the per-pixel mean of the samples, i.e. a box
-reconstruction: the library's film weighs the samples with the scene's reconstruction filter, so
-its image is a smoother version of this one.
+the built-in integrator's, bit for bit.  direct_image takes the per-pixel mean of the samples, i.e.
+a box reconstruction.  direct_film (--film) hands each sample, at its own position pixel + jitter
+(draws 0, 1 of sample_uniforms), to the library's film, which weighs it with the scene's
+reconstruction filter: the same terms the built-in integrator adds, so the developed image is the
+built-in render's up to the order of the film's additions.
 
 The library runs on its own stream and its calls block, so the only synchronisation needed is
 torch.cuda.synchronize() before a call that reads what torch has just written.
@@ -127,6 +130,26 @@ def direct_image(r, integrator="mis", spp=1, seed=0):
     return (total / spp).reshape(scene.height, scene.width, 3)
 
 
+def direct_film(r, integrator="mis", spp=1, seed=0):
+    """(H+2b, W+2b, 4) float32 cuda tensor: the RGBW film of passes 0 .. spp-1, each sample put at
+    pixel + its jitter through the scene's reconstruction filter (nori_amd.develop turns it into the image)."""
+    scene = r.scene
+    dev = torch.device("cuda", r.device)
+    H, W = scene.height, scene.width
+    film = torch.zeros(scene.film_shape(), dtype=torch.float32, device=dev)
+    ys, xs = torch.meshgrid(torch.arange(H, device=dev), torch.arange(W, device=dev), indexing="ij")
+    pixel = torch.stack([xs, ys], -1).float()
+    jitter = torch.zeros((1, H, W, 2), dtype=torch.float32, device=dev)
+    for k in range(spp):
+        L = sample_radiance(r, integrator, k, seed).contiguous()
+        torch.cuda.synchronize(dev)
+        r.sample_uniforms(0, 2, passes=1, pass_begin=k, seed=seed, out=jitter)
+        pos = (pixel + jitter[0]).contiguous()  # (float)x + u0, (float)y + u1: the reference's pixelSample
+        torch.cuda.synchronize(dev)
+        r.film_splat_passes(pos, L, passes=1, out=film)
+    return film
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("scene")
@@ -136,10 +159,14 @@ def main():
     ap.add_argument("--width", type=int, default=0)
     ap.add_argument("--height", type=int, default=0)
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--film", action="store_true", help="filter the samples into the library's film instead of the box mean")
     a = ap.parse_args()
     scene = nori_amd.load_scene(a.scene, a.width, a.height, 1)
     with nori_amd.GpuRenderer(scene, a.device) as r:
-        img = direct_image(r, a.integrator, a.spp).cpu().numpy()  # the first host copy
+        if a.film:
+            img = nori_amd.develop(scene, direct_film(r, a.integrator, a.spp).cpu().numpy())
+        else:
+            img = direct_image(r, a.integrator, a.spp).cpu().numpy()  # the first host copy
     nori_amd.write_png(a.output, img)
     print(f"{a.output}: {scene.width}x{scene.height}, direct_{a.integrator}, {a.spp} spp, mean {img.mean():.4f}")
 

@@ -761,6 +761,78 @@ int nori_gpu_emitter_eval(nori_gpu_ctx *ctx, const nori_gpu_shading_desc *desc, 
 int nori_gpu_sample_uniforms(nori_gpu_ctx *ctx, const nori_gpu_render_desc *desc, uint32_t first,
                              uint32_t count, float *out);
 
+/* ---- film splat: caller-supplied samples filtered into the film ----
+ * (no reference counterpart as an API: it is ImageBlock::put(pos, value)
+ * followed by put(block), the step the built-in integrators end with;
+ * deviation D17)
+ * The statement, on the host.  pos: n x 2 floats, the sample position in pixel
+ * units (the reference's pixelSample; for the renderer's own samples
+ * (float)x + u0, (float)y + u1 with u0, u1 draws 0 and 1 of
+ * nori_gpu_sample_uniforms); val: n x 3 floats; rgbw: (H+2b) x (W+2b) x 4,
+ * ADDED into; stats: NULL or H x W x 8, added into, laid out as
+ * nori_gpu_render_desc.variance_out.  For each sample i, in index order:
+ *  1. Owner pixel (x, y).  ordered == 0: (floor(pos.x), floor(pos.y)).
+ *     ordered != 0: n is a multiple of H W and the owner is pixel i mod (H W),
+ *     the layout of nori_gpu_camera_rays (pass k at k H W + y W + x); the
+ *     position must lie in the closed square [x, x+1] x [y, y+1] (closed:
+ *     (float)x + u can round up to x + 1).
+ *  2. The sample is dropped and counted in counts[1] if the position is not
+ *     finite, the owner is outside the frame, (ordered) the position is
+ *     outside the owner's square, or val fails Color3f::isValid (a channel
+ *     negative or not finite).
+ *  3. Otherwise it is counted in counts[0] and put into the owner's 32x32
+ *     frame block (block.cpp:93-122), origin (ox, oy), size bw x bh (smaller
+ *     at the frame's edge): px = pos.x - 0.5f - (float)(ox - b), py likewise;
+ *     the window runs from ceil(px - radius) to floor(px + radius), clipped to
+ *     the block's own tile [0, bw + 2b - 1] (and [0, bh + 2b - 1]); the
+ *     weights are table[min((int)(fabsf((float)c - px) * lookup),
+ *     NORI_FILTER_RESOLUTION)], lookup = NORI_FILTER_RESOLUTION / radius; cell
+ *     (ox + cx, oy + cy) of rgbw receives (val.c * wx) * wy for c = r, g, b and
+ *     (1.0f * wx) * wy -- each a single float operation in the order written.
+ *  4. With stats, the owner's floats 0..6 receive L.r, L.g, L.b, L.r L.r,
+ *     L.g L.g, L.b L.b and 1.
+ * The device calls below produce the same terms bit for bit and may differ
+ * only in the order of the additions.  NORI_ERR_INVALID: a null argument
+ * (stats may be NULL), ordered with n not a multiple of H W. */
+int nori_film_splat(const nori_scene_desc *scene, uint64_t n, int ordered, const float *pos,
+                    const float *val, float *rgbw, float *stats, uint64_t counts[2]);
+
+typedef struct nori_gpu_splat_desc {
+    uint64_t n;                   /* samples                                   */
+    int32_t on_device;            /* pos, val, rgbw and variance_out are device
+                                     memory on the context's device            */
+    uint32_t reserved;            /* must be 0                                 */
+    float *variance_out;          /* optional H x W x 8, added into            */
+} nori_gpu_splat_desc;
+
+/* nori_film_splat on the context's device, for a context of any integrator and
+ * traversal mode.  Device arrays are used in place (pos and val 4-byte, rgbw
+ * and variance_out 16-byte aligned, all checked to be device memory); host
+ * arrays are staged through context-owned buffers in chunks of at most
+ * NORI_QUERY_CHUNK samples (the passes layout: whole passes, at least one), and
+ * a host film is accumulated on the device and added into the caller's array
+ * once, as nori_gpu_render does.  stats (may be NULL): samples = splatted,
+ * invalid_samples = dropped, ms_total, ms_splat = HIP-event time of the
+ * kernels.  Blocking, on the context's stream.  A refusal launches nothing and
+ * leaves the context usable.
+ * nori_gpu_film_splat: samples anywhere on the image, nori_film_splat with
+ * ordered = 0.  n == 0 is a no-op.  NORI_ERR_INVALID: a null argument, reserved
+ * != 0, a device pointer that is misaligned or not device memory. */
+int nori_gpu_film_splat(nori_gpu_ctx *ctx, const nori_gpu_splat_desc *desc, const float *pos,
+                        const float *val, float *rgbw, nori_gpu_stats *stats);
+/* nori_gpu_film_splat_passes: samples in the layout of nori_gpu_camera_rays,
+ * nori_film_splat with ordered = 1 -- pos: pass_count x H x W x 2, val:
+ * pass_count x H x W x 3.  From `desc`: pass_count (0 = the scene's
+ * sampleCount), num_blocks / block_ids (only the selected blocks' pixels are
+ * read and splatted, the rest of a device array is never touched),
+ * output_on_device (which covers pos, val, rgbw and variance_out) and
+ * variance_out; pass_begin, seed, path_pool and timing are ignored.
+ * NORI_ERR_INVALID: a null argument, a block id out of range, no passes (both
+ * pass_count and the scene's sampleCount 0), a device pointer that is
+ * misaligned or not device memory. */
+int nori_gpu_film_splat_passes(nori_gpu_ctx *ctx, const nori_gpu_render_desc *desc, const float *pos,
+                               const float *val, float *rgbw, nori_gpu_stats *stats);
+
 /* ---- dynamic geometry: new vertex positions, the BVH refitted on the device ----
  * (no reference counterpart: the reference builds its BVH once, in
  * Scene::activate; deviation D14) */

@@ -1,7 +1,7 @@
 // ctx.h -- the runtime units' private view of a context: nori_gpu_ctx and
 // nori_gpu_comm, device buffers, HIP error handling, and the few functions
 // that cross units.  Included by upload.hip, render.hip, queries.hip,
-// adaptive.hip, dynamic.hip and sharded.hip only.
+// film_splat.hip, adaptive.hip, dynamic.hip and sharded.hip only.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -92,6 +92,7 @@ struct nori_gpu_ctx {
     DevBuf nodes, prims, tri_vidx, pos, nrm, prim_shape, shapes, bsdfs, emitters, cdf, env, blob, plane_c, plane_f;
     DevBuf tex;          // ImageTexture / NormalMap texels (RGBX8), global memory
     uint32_t spp = 1;    // the scene's sampleCount (default pass count)
+    uint32_t scene_spp = 0;  // ... as the scene gives it (0 stays 0: nori_gpu_film_splat_passes has no array to size by 1)
     int stack = 8;       // traversal of extend/shadow: 0 = wave-uniform scan, else LDS stack depth
     uint32_t bvh_depth = 0, bvh_nodes = 0, num_prims = 0;
     size_t scene_bytes = 0;
@@ -112,6 +113,7 @@ struct nori_gpu_ctx {
     DevBuf q_rays, q_hits, q_surf;
     hipEvent_t q_ev[3] = {};
     // the shading queries (nori_gpu_bsdf_eval ..): staging of up to three host input arrays and the output
+    // (nori_gpu_film_splat*: sh_in[0] / sh_in[1] stage host positions and values, q_ev[0..1] time the kernels)
     DevBuf sh_in[3], sh_out;
     DevBuf ph, ph_rgbe, ph_tab, ph_start;             // photonmapper: photon map (photon_map.cpp) and its hash-grid buckets
     // nori_gpu_update_vertices: the refit schedule (host copy of its level bounds, device copy of
@@ -210,5 +212,6 @@ inline void scene_stats(const nori_gpu_ctx &c, std::chrono::steady_clock::time_p
 int bvh_stack_for(uint32_t depth, int forced);                                                         // upload.hip
 void work_lists(nori_gpu_ctx &c, const nori_gpu_render_desc &rd);                                       // render.hip
 int render(nori_gpu_ctx &c, const nori_gpu_render_desc &rd, float *rgbw_out, nori_gpu_stats *stats);   // render.hip
+uint32_t query_chunk();  // queries.hip: NORI_QUERY_CHUNK, the most elements of a host array staged at once
 
 }  // namespace nori

@@ -12,6 +12,8 @@
 // nori_film_features: first-hit feature sums -> per-pixel means.
 // nori_film_denoise_guided: the feature-guided denoiser in double precision
 //   (host statement of k_guided, denoise.hip).
+// nori_film_splat: caller-supplied samples filtered into the film (the host
+//   statement of k_splat_pos / k_splat_scatter, kernels_film.hip).
 #include <zlib.h>
 
 #include <algorithm>
@@ -20,7 +22,8 @@
 #include <cstring>
 #include <vector>
 
-#include "host_scene.h"
+#include "film_put.h"
+#include "scene_prep.h"
 
 namespace {
 
@@ -212,4 +215,55 @@ extern "C" int nori_film_denoise_guided(const float *rgb, const float *variance,
             for (int c = 0; c < 3; ++c) out[3 * p + c] = (float)(acc[c] / wsum);
         }
     return NORI_OK;
+}
+
+// ImageBlock::put(pos, value) of caller-supplied samples, stated at its
+// declaration (nori_gpu.h); the device versions are k_splat_pos and
+// k_splat_scatter (kernels_film.hip), which share film_put.h with it.
+extern "C" int nori_film_splat(const nori_scene_desc *scene, uint64_t n, int ordered, const float *pos, const float *val,
+                               float *rgbw, float *stats, uint64_t counts[2]) {
+    return nori::guarded([&] {
+        using namespace nori;
+        if (!scene || !pos || !val || !rgbw || !counts) return fail(NORI_ERR_INVALID, "null argument");
+        const int W = scene->camera.width, H = scene->camera.height;
+        if (W <= 0 || H <= 0) return fail(NORI_ERR_INVALID, "nori_film_splat: an empty frame");
+        const uint64_t WH = (uint64_t)W * (uint64_t)H;
+        if (ordered && n % WH != 0) return fail(NORI_ERR_INVALID, "nori_film_splat: ordered with n not a multiple of H * W");
+        FilmGeom F{};
+        F.W = W, F.H = H, F.B = film_border(scene->camera);
+        F.rad = scene->camera.filter_radius;
+        F.lk = NORI_FILTER_RESOLUTION / scene->camera.filter_radius;
+        filter_table(scene->camera, F.filter);
+        const int FW = W + 2 * F.B;
+        counts[0] = counts[1] = 0;
+        for (uint64_t i = 0; i < n; ++i) {
+            const uint64_t pix = i % WH;
+            const float r = val[3 * i], g = val[3 * i + 1], b = val[3 * i + 2];
+            PutWindow w;
+            if (!film_window(F, ordered != 0, (int)(pix % (uint64_t)W), (int)(pix / (uint64_t)W), pos[2 * i], pos[2 * i + 1], w) ||
+                !film_color_valid(r, g, b)) {
+                ++counts[1];
+                continue;
+            }
+            ++counts[0];
+            if (stats) {
+                float *v = stats + 8 * ((size_t)w.y * W + w.x);
+                v[0] += r, v[1] += g, v[2] += b;
+                v[3] += r * r, v[4] += g * g, v[5] += b * b;
+                v[6] += 1.0f;
+            }
+            for (int cy = w.y0; cy <= w.y1; ++cy) {
+                const float wy = film_weight(F.filter, F.lk, cy, w.py);
+                for (int cx = w.x0; cx <= w.x1; ++cx) {
+                    const float wx = film_weight(F.filter, F.lk, cx, w.px);
+                    float *f = rgbw + 4 * ((size_t)(w.oy + cy) * FW + (w.ox + cx));
+                    f[0] += (r * wx) * wy;
+                    f[1] += (g * wx) * wy;
+                    f[2] += (b * wx) * wy;
+                    f[3] += (1.0f * wx) * wy;
+                }
+            }
+        }
+        return NORI_OK;
+    });
 }

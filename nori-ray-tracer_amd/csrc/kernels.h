@@ -4,13 +4,15 @@
 // in kernels_features.hip; launch_surface and launch_camera_rays in
 // kernels_query.hip; the shading queries in kernels_shading.hip; the
 // denoisers, the block error and the refit in denoise.hip, block_error.hip
-// and refit.hip; all others in kernels.hip.
+// and refit.hip; the caller-fed film splats in kernels_film.hip; all others in
+// kernels.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <string>
 #include <vector>
 
+#include "film_put.h"
 #include "kernel_config.h"
 
 namespace nori {
@@ -25,6 +27,11 @@ constexpr int kTraceSpill = 64;    // traversal stack entries beyond the LDS par
 // NORI_STACK_KEYS each entry is a (child ref, entry distance) pair.
 constexpr int stack_lds_entries(int stack) { return NORI_STACK_KEYS ? stack / 2 : stack; }
 constexpr int kSplatBlock = 256;
+// The scattered film splat's default form (kernels_film.hip k_splat_scatter;
+// measured in DESIGN.md D17)
+#ifndef NORI_SCATTER_ROWS
+#define NORI_SCATTER_ROWS 1
+#endif
 #ifndef NORI_SCAN_RAYS
 #define NORI_SCAN_RAYS 2
 #endif
@@ -190,6 +197,23 @@ hipError_t launch_sample_uniforms(const DevScene &S, const uint32_t *pixels, uin
                                   hipStream_t st);
 hipError_t launch_splat(const DevScene &S, const float4 *rec, const SplatDesc &sd, uint32_t nblocks, float *film,
                         Counters *C, hipStream_t st);
+// Caller-supplied samples into the film (kernels_film.hip; stated at
+// nori_film_splat in nori_gpu.h).  All pointers are device memory; *dropped +=
+// the samples the statement drops.  film: (H+2B) x (W+2B) x 4 and var (or null):
+// H x W x 8, both added into with float atomics.
+// The passes layout (ordered): pass k < passes of the pixels of `blocks`
+// (work_lists' (ox, oy, bw | bh << 16, .)), the sample of pixel (x, y) at
+// pos[2 i], val[3 i] with i = k * stride + y * W + x; a work-group folds
+// passes_per_wg passes (>= 1, at most 65535 pass ranges).
+hipError_t launch_splat_pos(const FilmGeom &F, const int4 *blocks, uint32_t nblocks, uint32_t passes,
+                            uint32_t passes_per_wg, uint64_t stride, const float *pos, const float *val, float *film,
+                            float *var, unsigned long long *dropped, hipStream_t st);
+// Samples i < n anywhere on the image (the owner is the floor of the position);
+// rows: a wave walks its samples and adds whole window rows per instruction,
+// else one lane per sample (k_splat_scatter).
+constexpr bool kScatterRows = NORI_SCATTER_ROWS != 0;
+hipError_t launch_splat_scatter(const FilmGeom &F, uint64_t n, bool rows, const float *pos, const float *val,
+                                float *film, float *var, unsigned long long *dropped, hipStream_t st);
 // The adaptive sampler's block error (block_error.hip; the metric is stated
 // at nori_film_block_error in nori_gpu.h): stats W x H x 8 on the device
 // (16-byte aligned), ids = the nblocks frame blocks to evaluate (null: blocks

@@ -93,9 +93,8 @@ int render_features(nori_gpu_ctx &c, const nori_gpu_render_desc &rd, float *feat
     return NORI_OK;
 }
 
-// nori_gpu_query: launch_trace (the kernels of nori_gpu_trace), then k_surface
-// on its hits.  Device buffers are used in place; host arrays pass through the
-// context's staging buffers in chunks of at most NORI_QUERY_CHUNK rays.
+}  // namespace
+// NORI_QUERY_CHUNK: the most elements of a host array staged at once (ctx.h; film_splat.hip reads it too)
 uint32_t query_chunk() {
     if (const char *e = std::getenv("NORI_QUERY_CHUNK")) {
         const long long v = std::atoll(e);
@@ -103,6 +102,10 @@ uint32_t query_chunk() {
     }
     return 1u << 22;
 }
+namespace {
+// nori_gpu_query: launch_trace (the kernels of nori_gpu_trace), then k_surface
+// on its hits.  Device buffers are used in place; host arrays pass through the
+// context's staging buffers in chunks of at most NORI_QUERY_CHUNK rays.
 int query(nori_gpu_ctx &c, const nori_gpu_query_desc &qd, const float *rays, nori_gpu_hit *hits,
           nori_gpu_surface *surf, nori_gpu_stats *stats) {
     const auto t0 = std::chrono::steady_clock::now();

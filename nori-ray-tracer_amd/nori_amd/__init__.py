@@ -27,7 +27,7 @@ from ._abi import NoriError, check, lib  # noqa: F401
 __all__ = ["load_scene", "Scene", "GpuRenderer", "RenderThread", "NoriError", "device_count",
            "develop", "write_exr", "write_png", "read_exr", "film_variance", "ldr_bytes", "variance_gray",
            "denoise", "read_image", "block_error", "film_features", "denoise_guided", "film_denoise_guided",
-           "scene_surface", "bvh_refit", "bvh_rebuild"]
+           "scene_surface", "bvh_refit", "bvh_rebuild", "film_splat"]
 
 
 def _fptr(a):
@@ -160,6 +160,31 @@ def film_variance(scene, stats):
     out = np.zeros((scene.height, scene.width, 3), np.float32)
     check(lib().nori_film_variance(scene.desc_ptr, _fptr(stats), _fptr(out)))
     return out
+
+
+def film_splat(scene, pos, val, ordered=False, out=None, variance=None):
+    """Caller-supplied samples filtered into the film on the host (nori_film_splat, where the
+    operation is stated): pos (n, 2) sample positions in pixel units, val (n, 3) radiance.
+    ordered: the layout of camera_rays() / sample_uniforms() -- sample i belongs to pixel
+    i mod (H W) and must lie in its closed square.  Returns (film, (splatted, dropped)): the RGBW
+    film (H+2b, W+2b, 4), added into `out` when given.  `variance`: an (H, W, 8) float32 array the
+    owner pixels' sample statistics are added into (see film_variance).
+    GpuRenderer.film_splat and film_splat_passes are the device versions."""
+    pos = np.ascontiguousarray(pos, dtype=np.float32).reshape(-1, 2)
+    val = np.ascontiguousarray(val, dtype=np.float32).reshape(-1, 3)
+    if pos.shape[0] != val.shape[0]:
+        raise ValueError(f"film_splat: {pos.shape[0]} positions and {val.shape[0]} values")
+    if out is None:
+        out = np.zeros(scene.film_shape(), np.float32)
+    assert out.dtype == np.float32 and out.flags.c_contiguous and out.shape == scene.film_shape()
+    if variance is not None:
+        assert (isinstance(variance, np.ndarray) and variance.dtype == np.float32 and variance.flags.c_contiguous
+                and variance.shape == (scene.height, scene.width, 8))
+    counts = (C.c_uint64 * 2)()
+    check(lib().nori_film_splat(scene.desc_ptr, pos.shape[0], int(bool(ordered)), C.c_void_p(pos.ctypes.data),
+                                C.c_void_p(val.ctypes.data), C.c_void_p(out.ctypes.data),
+                                None if variance is None else C.c_void_p(variance.ctypes.data), counts))
+    return out, (int(counts[0]), int(counts[1]))
 
 
 def block_error(scene, stats):
@@ -741,6 +766,73 @@ class GpuRenderer:
         assert out.dtype == np.float32 and out.flags.c_contiguous and out.shape == shape
         check(lib().nori_gpu_sample_uniforms(self._h, C.byref(rd), int(first), int(count), C.c_void_p(out.ctypes.data)))
         return out
+
+    def _splat_args(self, name, pos, val, n, out, variance):
+        """(on_device, n, pos, val, film, variance addresses, the film to return) of a film splat:
+        all numpy (host form) or all device addresses / torch tensors with a device film out=."""
+        def addr(a):
+            return int(a.data_ptr() if hasattr(a, "data_ptr") else a)
+        host = [isinstance(a, np.ndarray) for a in (pos, val)]
+        if any(host) != all(host):
+            raise ValueError(f"{name}: pos and val must both be numpy arrays or both be device addresses")
+        if not all(host):
+            if out is None or isinstance(out, np.ndarray) or isinstance(variance, np.ndarray):
+                raise ValueError(f"{name}: device arrays need a device film out= (and a device variance=)")
+            if n is None:
+                if not hasattr(val, "numel"):
+                    raise ValueError(f"{name}: int device addresses need the sample count")
+                n = val.numel() // 3
+            return 1, int(n), addr(pos), addr(val), addr(out), None if variance is None else addr(variance), None, ()
+        pos = np.ascontiguousarray(pos, dtype=np.float32).reshape(-1, 2)
+        val = np.ascontiguousarray(val, dtype=np.float32).reshape(-1, 3)
+        if pos.shape[0] != val.shape[0]:
+            raise ValueError(f"{name}: {pos.shape[0]} positions and {val.shape[0]} values")
+        if n is not None and int(n) != pos.shape[0]:
+            raise ValueError(f"{name}: {pos.shape[0]} samples, expected {int(n)}")
+        if out is None:
+            out = np.zeros(self.scene.film_shape(), np.float32)
+        assert (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.flags.c_contiguous
+                and out.shape == self.scene.film_shape())
+        if variance is not None:
+            assert (isinstance(variance, np.ndarray) and variance.dtype == np.float32 and variance.flags.c_contiguous
+                    and variance.shape == (self.scene.height, self.scene.width, 8))
+        return (0, pos.shape[0], pos.ctypes.data, val.ctypes.data, out.ctypes.data,
+                None if variance is None else variance.ctypes.data, out, (pos, val))
+
+    def film_splat(self, pos, val, n=None, out=None, variance=None):
+        """Samples anywhere on the image filtered into the film (nori_gpu_film_splat; the operation
+        is stated at nori_film_splat in nori_gpu.h): pos (n, 2) positions in pixel units, val (n, 3)
+        radiance; the owner pixel of a sample is the floor of its position.  With numpy arrays the
+        RGBW film (H+2b, W+2b, 4) is returned, added into `out` when given, and `variance` is an
+        (H, W, 8) float32 array for the owner pixels' sample statistics.  With torch tensors or int
+        device addresses (then with n=), `out` must be a device film (16-byte aligned, like
+        `variance`), everything is used in place and None is returned; the buffers must be ready
+        before the call.  last_stats: samples = splatted, invalid_samples = dropped, ms_splat."""
+        dev, n, p, v, film, var, ret, keep = self._splat_args("film_splat", pos, val, n, out, variance)
+        sd = _abi.SplatDesc(n, dev, 0, var)
+        st = _abi.Stats()
+        check(lib().nori_gpu_film_splat(self._h, C.byref(sd), C.c_void_p(p), C.c_void_p(v), C.c_void_p(film), C.byref(st)))
+        self.last_stats = st.as_dict()
+        return ret
+
+    def film_splat_passes(self, pos, val, passes=None, blocks=None, out=None, variance=None):
+        """Samples in the layout of camera_rays() / sample_uniforms() filtered into the film
+        (nori_gpu_film_splat_passes): pos (passes, H, W, 2) with the sample of pass k and pixel
+        (x, y) inside the closed square [x, x+1] x [y, y+1] -- for the renderer's own samples
+        pixel + sample_uniforms(0, 2) in float32 -- and val (passes, H, W, 3).  Only the pixels of
+        `blocks` (all if None) are read.  Host and device forms, `out`, `variance` and last_stats
+        as film_splat."""
+        rd, ids = self._desc(passes, 0, blocks, 0, 0, False)
+        # (pass_count 0 is the library's "the scene's sampleCount"; a scene of 0 spp is refused there)
+        n = rd.pass_count * self.scene.width * self.scene.height if rd.pass_count else None
+        dev, n, p, v, film, var, ret, keep = self._splat_args("film_splat_passes", pos, val, n, out, variance)
+        rd.output_on_device = dev
+        rd.variance_out = var
+        st = _abi.Stats()
+        check(lib().nori_gpu_film_splat_passes(self._h, C.byref(rd), C.c_void_p(p), C.c_void_p(v), C.c_void_p(film),
+                                               C.byref(st)))
+        self.last_stats = st.as_dict()
+        return ret
 
     def _vertex_arg(self, a, what):
         """(address, on_device, keep-alive) of a positions / normals argument of update_vertices."""

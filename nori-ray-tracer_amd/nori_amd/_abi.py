@@ -143,6 +143,11 @@ class ShadingDesc(C.Structure):
     _fields_ = [("n", C.c_uint32), ("on_device", C.c_int32), ("emitter", C.c_int32), ("reserved", C.c_uint32)]
 
 
+class SplatDesc(C.Structure):
+    """nori_gpu_splat_desc: the descriptor of nori_gpu_film_splat."""
+    _fields_ = [("n", C.c_uint64), ("on_device", C.c_int32), ("reserved", C.c_uint32), ("variance_out", C.c_void_p)]
+
+
 class UpdateDesc(C.Structure):
     """nori_gpu_update_desc: new vertex positions (and normals) for nori_gpu_update_vertices."""
     _fields_ = [("positions", C.c_void_p), ("normals", C.c_void_p), ("num_vertices", C.c_uint32),
@@ -225,6 +230,12 @@ SIGNATURES = {
                                           C.c_void_p]),
     "nori_gpu_emitter_eval": (C.c_int, [C.c_void_p, C.POINTER(ShadingDesc), C.c_void_p, C.c_void_p, C.c_void_p]),
     "nori_gpu_sample_uniforms": (C.c_int, [C.c_void_p, C.POINTER(RenderDesc), C.c_uint32, C.c_uint32, C.c_void_p]),
+    "nori_film_splat": (C.c_int, [C.POINTER(SceneDesc), C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.POINTER(C.c_uint64)]),
+    "nori_gpu_film_splat": (C.c_int, [C.c_void_p, C.POINTER(SplatDesc), C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.POINTER(Stats)]),
+    "nori_gpu_film_splat_passes": (C.c_int, [C.c_void_p, C.POINTER(RenderDesc), C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.POINTER(Stats)]),
     "nori_gpu_update_vertices": (C.c_int, [C.c_void_p, C.POINTER(UpdateDesc), C.POINTER(UpdateStats)]),
     "nori_gpu_bvh_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint32)]),
     "nori_scene_bvh_refit": (C.c_int, [C.POINTER(SceneDesc), C.POINTER(C.c_float), C.POINTER(C.c_float),
@@ -253,7 +264,8 @@ SIGNATURES = {
 ADDED_IN_7 = {"nori_gpu_query", "nori_scene_surface", "nori_gpu_camera_rays", "nori_gpu_update_vertices",
               "nori_gpu_bvh_read", "nori_scene_bvh_refit", "nori_scene_bvh_rebuild", "nori_gpu_rebuild_bvh",
               "nori_scene_shade_rtc", "nori_gpu_shade_rtc_info", "nori_gpu_bsdf_eval", "nori_gpu_bsdf_sample",
-              "nori_gpu_emitter_sample", "nori_gpu_emitter_eval", "nori_gpu_sample_uniforms"}
+              "nori_gpu_emitter_sample", "nori_gpu_emitter_eval", "nori_gpu_sample_uniforms", "nori_film_splat",
+              "nori_gpu_film_splat", "nori_gpu_film_splat_passes"}
 
 COMM_ID_BYTES = 128
 SHARD_PASSES, SHARD_BLOCKS = 0, 1
