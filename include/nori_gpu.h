@@ -392,6 +392,16 @@ typedef struct nori_scan_info {
 int nori_scene_scan_list(const nori_scene_desc *scene, nori_scan_info *info, float *records, float *plane_c,
                          float *plane_f);
 
+/* The bound of the fast body that both hipRTC programs below carry for this
+ * scene: a wave whose rays all have |o_x| + |o_y| + |o_z| + |d_x| + |d_y| +
+ * |d_z| <= *fast_max and mint > 0 scans the scene's literal records without
+ * the per-test range checks and without the products whose record factor is
+ * zero (same hits, t and primitive ids bit for bit; u, v equal as values);
+ * every other wave takes the checked body.  0: the programs are built without
+ * it -- a BVH scene, a scan list whose coordinates leave the bound no room, or
+ * NORI_SCAN_FAST=0.  (Added without an ABI bump.) */
+int nori_scene_scan_fast(const nori_scene_desc *scene, float *fast_max);
+
 /* Compiles the scene's scan kernels specialised for its scan list (the
  * hipRTC program nori_gpu_create loads for scan-mode scenes, rtc.hip) for the
  * target `arch` (e.g. "gfx950"), without a device: *code_bytes = the code

@@ -60,6 +60,7 @@ struct ScanRtcScene {
     uint32_t pairs;
     uint32_t plane_end[3];
     uint32_t tris, real;
+    float fast_max;  // the bound of scan.h's fast body (scene_prep.h scan_fast_max), 0: none
 };
 struct ScanRtc {
     hipModule_t mod = nullptr;

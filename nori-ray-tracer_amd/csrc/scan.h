@@ -7,7 +7,9 @@
 // from DevScene, and at context creation through hipRTC (rtc.cpp) with
 // NORI_CONST_SCENE and the scene's generated const_scene.h, so that the
 // records are literal operands of the tests -- no scalar loads, no waits on
-// them, and the compiler folds what the records make constant.
+// them, and the compiler folds what the records make constant.  That build
+// also carries the scans' fast body (below scan_core), which the other never
+// compiles.
 #pragma once
 #include "dev_scene.h"
 
@@ -43,6 +45,22 @@ ND bool box_test(const float4 &mn, const float4 &mx, const TRay &r, float &tnear
 
 // 1 / det of the triangle tests, correctly rounded (== 1.0f / det, tools/rcp_check.hip).
 ND float rcp_det(float x) { return rcp_rn(x); }
+// rcp_rn without its range check, for |x| <= 2^125 known beforehand (NaN
+// excluded); below 2^-125 no caller uses the value, as in rcp_rn.
+ND float rcp_core(float x) {
+#ifdef __HIP_DEVICE_COMPILE__
+    const float r = __builtin_amdgcn_rcpf(x);
+    const float e = __builtin_fmaf(-x, r, 1.0f);
+    return __builtin_fmaf(e, r, r);
+#else
+    return 1.0f / x;
+#endif
+}
+// rcp_full for |x| <= 2^125 known beforehand (NaN excluded): the lower check only.
+ND float rcp_full_lo(float x) {
+    if (__builtin_expect(!(__builtin_fabsf(x) >= 0x1p-125f), 0)) return 1.0f / x;
+    return rcp_core(x);
+}
 // Mesh::rayIntersect (mesh.cpp:83-120), edges precomputed exactly.
 ND bool tri_hit(const float4 &a, const float4 &b, const float4 &c, const TRay &r, float &t, float &u, float &v) {
     V3 v0 = ld3(a), e1 = ld3(b), e2 = ld3(c);
@@ -156,6 +174,9 @@ ND bool sphere_hit_nb(const float4 &a, const float4 &b, const TRay &r, float &t)
 #define NORI_SPHERE_FAST 1
 #endif
 ND bool in_range60(float x) { return fabsf(x) >= 0x1p-60f && fabsf(x) <= 0x1p60f; }
+// NOCHECK (the scene's fast body below): y = 2 d.d is within rcp_rn's range,
+// so its core runs unchecked.
+template <bool NOCHECK = false>
 ND bool sphere_hit_fast(const float4 &a, const float4 &b, const TRay &r, float &t) {
     if (!NORI_SPHERE_FAST) return sphere_hit_nb(a, b, r, t);
     V3 oc = r.o - ld3(a);
@@ -170,7 +191,9 @@ ND bool sphere_hit_fast(const float4 &a, const float4 &b, const TRay &r, float &
     const float sd = __uint_as_float(__float_as_uint(s0) - 1u), su = __uint_as_float(__float_as_uint(s0) + 1u);
     const float rd = __builtin_fmaf(-sd, s0, disc), ru = __builtin_fmaf(-su, s0, disc);
     float delta = ru > 0.0f ? su : (rd <= 0.0f ? sd : s0);
-    const float ry = rcp_rn(y);
+    float ry;
+    if constexpr (NOCHECK) ry = rcp_core(y);
+    else ry = rcp_rn(y);
     float x1 = -B - delta, x2 = -B + delta;
     float q1 = x1 * ry, q2 = x2 * ry;
     float t1 = __builtin_fmaf(__builtin_fmaf(-y, q1, x1), ry, q1), t2 = __builtin_fmaf(__builtin_fmaf(-y, q2, x2), ry, q2);
@@ -201,7 +224,7 @@ ND bool sphere_hit_fast(const float4 &a, const float4 &b, const TRay &r, float &
 // per group), then the spheres.  The root box test of bvh.cpp:420 is kept so
 // rays missing the scene never report hits.  K rays per thread share every
 // fetched record.
-template <int K>
+template <int K, bool BOUNDED = false>  // BOUNDED: the fast body's rays (below)
 ND void scan_prologue(const DevScene &S, TRay (&r)[K], bool (&live)[K]) {
     const float4 rmn = make_float4(S.root_min[0], S.root_min[1], S.root_min[2], 0.f);
     const float4 rmx = make_float4(S.root_max[0], S.root_max[1], S.root_max[2], 0.f);
@@ -209,7 +232,8 @@ ND void scan_prologue(const DevScene &S, TRay (&r)[K], bool (&live)[K]) {
     for (int k = 0; k < K; ++k) {
         TRay &x = r[k];
         if (x.mint == kEps) x.mint = smax(x.mint, x.mint * smax(smax(fabsf(x.o.x), fabsf(x.o.y)), fabsf(x.o.z)));
-        x.rcp = V3{rcp_full(x.d.x), rcp_full(x.d.y), rcp_full(x.d.z)};
+        if constexpr (BOUNDED) x.rcp = V3{rcp_full_lo(x.d.x), rcp_full_lo(x.d.y), rcp_full_lo(x.d.z)};
+        else x.rcp = V3{rcp_full(x.d.x), rcp_full(x.d.y), rcp_full(x.d.z)};
         float tn;
         live[k] = live[k] && !(x.maxt < x.mint) && box_test(rmn, rmx, x, tn);
     }
@@ -430,6 +454,189 @@ ND void scan_core(const DevScene &S, TRay (&r)[K], bool (&live)[K], float (&tb)[
     }
 }
 
+#ifdef NORI_CONST_SCENE
+// ---- The fast body of the scene's own build (kScanFastMax > 0 in
+// const_scene.h).  A wave takes it when every live ray has
+//     |o_x| + |o_y| + |o_z| + |d_x| + |d_y| + |d_z| <= kScanFastMax,  mint > 0
+// (a NaN or an infinity anywhere fails the sum's comparison), so every
+// component of o and d is finite and at most M = kScanFastMax in magnitude.
+// Every other wave runs scan_core, unchanged.  The host chose M for this scan
+// list (scene_prep.cpp scan_fast_max) so that, for such rays, every
+// intermediate of the triangle test -- tvec, pvec, qvec, det and the three
+// numerators -- is at most 2^125 in magnitude, hence finite, and 2 d.d of the
+// sphere test likewise.  Two things follow.
+// (a) 1 / det and the sphere's 1 / (2 d.d) are inside rcp_rn's verified range
+// (or below it, where neither test uses the value): rcp_core, no check, no
+// IEEE division behind it.  The prologue's 1 / d_i keeps its lower check only
+// (d_i may be zero or denormal).
+// (b) The records being literals, a product with an exactly zero edge
+// component is left out, and so is a product with a pvec or qvec component
+// whose two terms both went that way.  tri_hit_plane's argument, for every
+// literal zero: the other factor is finite, so the product is a signed zero;
+// in cross() and dot() it is added to or subtracted from other terms, which
+// keep their values (x +- 0 = x for x != 0), and the roundings of the terms
+// that remain are the same operations on the same values.  Only the sign of
+// an exactly zero intermediate or result can differ.  A zero det is rejected
+// whatever its sign (|det| < 1e-8) before its reciprocal, the one place a
+// zero's sign could turn into a value, is used; u = +-0 and v = +-0 compare
+// alike; t = +-0 < mint.  Hence hit or miss, t and the primitive id are
+// bit-identical to scan_core's, and u, v are equal as values.  (mint <= 0,
+// which the trace API allows, could accept t = +-0: such a wave fails the
+// guard.)  A record of two zero edges, the lists' padding, never hits (det =
+// 0) and is not tested at all.
+// (c) The acceptance predicate and the best-hit update are bitwise
+// combinations and selects.  With && and an `if`, the compiler sinks u, then
+// v and t, behind nested exec-mask branches that a wave of incoherent rays
+// never takes, and pays for them in scalar instructions and register moves;
+// this form leaves it nothing to sink.  The same values are selected, so the
+// results are those of the branching form.  (The shade kernel keeps its 78
+// VGPRs with it, no scratch.)
+ND bool scan_fast_ray(const TRay &r) {
+    const float s = ((((fabsf(r.o.x) + fabsf(r.o.y)) + fabsf(r.o.z)) + fabsf(r.d.x)) + fabsf(r.d.y)) + fabsf(r.d.z);
+    return s <= kScanFastMax && r.mint > 0.0f;
+}
+// a k1 - b k2, (a + b) + c with their literally zero terms left out
+template <bool Z1, bool Z2>
+ND float diff_nz(float a, float k1, float b, float k2) {
+    if constexpr (Z1 && Z2) return 0.0f;
+    else if constexpr (Z1) return -(b * k2);
+    else if constexpr (Z2) return a * k1;
+    else return a * k1 - b * k2;
+}
+template <bool Z0, bool Z1, bool Z2>
+ND float sum_nz(float a, float b, float c) {
+    if constexpr (Z0 && Z1 && Z2) return 0.0f;
+    else if constexpr (Z0 && Z1) return c;
+    else if constexpr (Z0 && Z2) return b;
+    else if constexpr (Z1 && Z2) return a;
+    else if constexpr (Z0) return b + c;
+    else if constexpr (Z1) return a + c;
+    else if constexpr (Z2) return a + b;
+    else return (a + b) + c;
+}
+// tri_hit_nb of record I
+template <uint32_t I>
+ND bool tri_hit_lit(const TRay &r, float &t, float &u, float &v) {
+    constexpr float e1x = kCRec[12 * I + 4], e1y = kCRec[12 * I + 5], e1z = kCRec[12 * I + 6];
+    constexpr float e2x = kCRec[12 * I + 8], e2y = kCRec[12 * I + 9], e2z = kCRec[12 * I + 10];
+    constexpr bool a0 = e1x == 0.0f, a1 = e1y == 0.0f, a2 = e1z == 0.0f;  // zero components of e1,
+    constexpr bool b0 = e2x == 0.0f, b1 = e2y == 0.0f, b2 = e2z == 0.0f;  // of e2,
+    constexpr bool p0 = b2 && b1, p1 = b0 && b2, p2 = b1 && b0;           // of pvec = d x e2
+    constexpr bool q0 = a2 && a1, q1 = a0 && a2, q2 = a1 && a0;           // and of qvec = tvec x e1
+    const V3 d = r.d, tv = r.o - V3{kCRec[12 * I], kCRec[12 * I + 1], kCRec[12 * I + 2]};
+    const float px = diff_nz<b2, b1>(d.y, e2z, d.z, e2y), py = diff_nz<b0, b2>(d.z, e2x, d.x, e2z),
+                pz = diff_nz<b1, b0>(d.x, e2y, d.y, e2x);
+    const float det = sum_nz<a0 || p0, a1 || p1, a2 || p2>(e1x * px, e1y * py, e1z * pz);
+    const float inv_det = rcp_core(det);
+    u = sum_nz<p0, p1, p2>(tv.x * px, tv.y * py, tv.z * pz) * inv_det;
+    const float qx = diff_nz<a2, a1>(tv.y, e1z, tv.z, e1y), qy = diff_nz<a0, a2>(tv.z, e1x, tv.x, e1z),
+                qz = diff_nz<a1, a0>(tv.x, e1y, tv.y, e1x);
+    v = sum_nz<q0, q1, q2>(d.x * qx, d.y * qy, d.z * qz) * inv_det;
+    t = sum_nz<b0 || q0, b1 || q1, b2 || q2>(e2x * qx, e2y * qy, e2z * qz) * inv_det;
+    // (c): tri_hit_nb's conjunction with & and | on the comparisons, so that no
+    // short-circuit is left for the compiler to sink the tests behind
+    return (int)!((det > -1e-8f) & (det < 1e-8f)) & (int)!((u < 0.0f) | (u > 1.0f)) & (int)!((v < 0.0f) | (u + v > 1.0f)) &
+           (int)(t >= r.mint) & (int)(t <= r.maxt);
+}
+// scan_tri for record I
+template <uint32_t I, int K, bool ANY>
+ND void scan_tri_lit(TRay (&r)[K], const bool (&live)[K], float (&tb)[K], uint32_t (&pb)[K], uint32_t (&lb)[K],
+                     float (&ub)[K], float (&vb)[K], bool (&found)[K]) {
+    constexpr bool e1_zero = kCRec[12 * I + 4] == 0.0f && kCRec[12 * I + 5] == 0.0f && kCRec[12 * I + 6] == 0.0f;
+    constexpr bool e2_zero = kCRec[12 * I + 8] == 0.0f && kCRec[12 * I + 9] == 0.0f && kCRec[12 * I + 10] == 0.0f;
+    if constexpr (!(e1_zero && e2_zero)) {
+        const uint32_t pos = __float_as_uint(kCRec[12 * I + 11]);
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            float t = 0, u = 0, v = 0;
+            const bool h = tri_hit_lit<I>(r[k], t, u, v);  // t <= r.maxt = tb
+            // scan_tri's update as selects (c): straight-line code for the whole test
+            const bool take = (int)h & (int)live[k] & ((int)ANY | (int)(t != tb[k]) | (int)(pos > lb[k]));
+            found[k] = (int)found[k] | (int)take;
+            if (!ANY) {
+                r[k].maxt = take ? t : r[k].maxt;  // (not tb: the ray's own maxt stands until the first hit)
+                tb[k] = take ? t : tb[k];
+                ub[k] = take ? u : ub[k];
+                vb[k] = take ? v : vb[k];
+                pb[k] = take ? __float_as_uint(kCRec[12 * I + 3]) : pb[k];
+                lb[k] = take ? pos : lb[k];
+            }
+        }
+    }
+}
+// scan_planes for the pairs [G, G1) of axis A
+template <uint32_t G, uint32_t G1, int A, int K, bool ANY, int CULL>
+ND void scan_planes_lit(TRay (&r)[K], const bool (&live)[K], float (&tb)[K], uint32_t (&pb)[K], uint32_t (&lb)[K],
+                        float (&ub)[K], float (&vb)[K], bool (&found)[K]) {
+    if constexpr (G < G1) {
+        bool may = true;
+        if constexpr (CULL == 2) {
+            constexpr int B = (A + 1) % 3, C = (A + 2) % 3;
+            const float4 f0 = cpf(2 * G), f1 = cpf(2 * G + 1);
+            may = false;
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
+                const float mlo = r[k].mint > 0.0f ? r[k].mint * kPlaneLo : -INF_F;
+                const float mhi = r[k].maxt > 0.0f ? r[k].maxt * kPlaneHi : INF_F;
+                const float so = fabsf(comp<B>(r[k].o)) + fabsf(comp<C>(r[k].o));
+                const float sd = fabsf(comp<B>(r[k].d)) + fabsf(comp<C>(r[k].d));
+                may = may || (live[k] && pair_candidate<A>(r[k], f0, f1, mlo, mhi, so, sd));
+            }
+        } else if constexpr (CULL != 0) {
+            may = false;
+#pragma unroll
+            for (int k = 0; k < K; ++k)
+                may = may || (live[k] && plane_may_hit(comp<A>(r[k].o), comp<A>(r[k].d), kCPlaneC[G], r[k].mint, r[k].maxt));
+        }
+        if (CULL == 0 || __any(may)) {
+            scan_tri_lit<2 * G, K, ANY>(r, live, tb, pb, lb, ub, vb, found);
+            scan_tri_lit<2 * G + 1, K, ANY>(r, live, tb, pb, lb, ub, vb, found);
+        }
+        scan_planes_lit<G + 1, G1, A, K, ANY, CULL>(r, live, tb, pb, lb, ub, vb, found);
+    }
+}
+template <int K>
+ND bool scan_all_done(const bool (&live)[K], const bool (&found)[K]) {
+    bool done = true;
+#pragma unroll
+    for (int k = 0; k < K; ++k) done = done && (found[k] || !live[k]);
+    return __all(done);
+}
+// the other triangles from record I on, group by group, then the spheres;
+// true: every ray of an any-hit wave has its hit
+template <uint32_t I, int K, bool ANY>
+ND bool scan_rest_lit(TRay (&r)[K], const bool (&live)[K], float (&tb)[K], uint32_t (&pb)[K], uint32_t (&lb)[K],
+                      float (&ub)[K], float (&vb)[K], bool (&found)[K]) {
+    if constexpr (I < kCTris) {
+        if constexpr (ANY && (I - 2 * kCPlaneEnd[2]) % kScanGroup == 0)  // (scan_core asks once per group)
+            if (scan_all_done<K>(live, found)) return true;
+        scan_tri_lit<I, K, ANY>(r, live, tb, pb, lb, ub, vb, found);  // (a padding record is skipped there)
+        return scan_rest_lit<I + 1, K, ANY>(r, live, tb, pb, lb, ub, vb, found);
+    } else if constexpr (I < kCPrims) {
+        if (ANY && scan_all_done<K>(live, found)) return true;
+        const float4 p0 = crec(3 * I), p1 = crec(3 * I + 1);
+        const uint32_t pos = __float_as_uint(kCRec[12 * I + 11]);
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            float t = 0;
+            const bool h = sphere_hit_fast<true>(p0, p1, r[k], t);  // t <= r.maxt = tb
+            if (h && live[k] && (ANY || t != tb[k] || pos > lb[k])) {
+                found[k] = true;
+                if (!ANY) {
+                    r[k].maxt = tb[k] = t;
+                    ub[k] = vb[k] = 0.0f;
+                    pb[k] = __float_as_uint(p0.w);
+                    lb[k] = pos;
+                }
+            }
+        }
+        return scan_rest_lit<I + 1, K, ANY>(r, live, tb, pb, lb, ub, vb, found);
+    } else {
+        return false;
+    }
+}
+#endif
+
 // Scan-mode traversal of K rays per thread: every primitive record is
 // fetched once (scalar loads) and tested against K independent rays, which
 // gives the VALU K independent dependency chains to interleave.  Results are
@@ -438,6 +645,30 @@ ND void scan_core(const DevScene &S, TRay (&r)[K], bool (&live)[K], float (&tb)[
 template <int K, bool ANY, int CULL = 1, bool ZMINT = false>
 ND void scan_rays(const DevScene &S, TRay (&r)[K], bool (&live)[K], float (&tb)[K], uint32_t (&pb)[K],
                   float (&ub)[K], float (&vb)[K], bool (&found)[K]) {
+#ifdef NORI_CONST_SCENE
+    if constexpr (kScanFastMax > 0.0f) {  // the fast body for the waves whose rays are all within its bound
+        bool in = true;
+#pragma unroll
+        for (int k = 0; k < K; ++k) in = in && (!live[k] || scan_fast_ray(r[k]));
+        if (__builtin_expect(__all(in), 1)) {
+            scan_prologue<K, true>(S, r, live);
+            uint32_t lb[K];
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
+                tb[k] = INF_F;
+                pb[k] = 0xFFFFFFFFu;
+                lb[k] = 0;
+                ub[k] = vb[k] = 0.0f;
+                found[k] = false;
+            }
+            scan_planes_lit<0, kCPlaneEnd[0], 0, K, ANY, CULL>(r, live, tb, pb, lb, ub, vb, found);
+            scan_planes_lit<kCPlaneEnd[0], kCPlaneEnd[1], 1, K, ANY, CULL>(r, live, tb, pb, lb, ub, vb, found);
+            scan_planes_lit<kCPlaneEnd[1], kCPlaneEnd[2], 2, K, ANY, CULL>(r, live, tb, pb, lb, ub, vb, found);
+            scan_rest_lit<2 * kCPlaneEnd[2], K, ANY>(r, live, tb, pb, lb, ub, vb, found);
+            return;
+        }
+    }
+#endif
     scan_core<K, ANY, CULL, ZMINT>(S, r, live, tb, pb, ub, vb, found);
 }
 

@@ -339,7 +339,41 @@ static bool axis_plane(const float *r, int a) {
     const double diff = std::fabs(P - Q);
     return diff > 0.0 && (std::fabs(P) + std::fabs(Q)) <= 32.0 * diff;
 }
+static ScanList build_scan_list_(const DeviceBvh &bvh, uint32_t n);
+float scan_fast_max(const ScanList &L) {
+    if (const char *e = std::getenv("NORI_SCAN_FAST"); e && e[0] == '0') return 0.0f;
+    // E: the largest edge component, V: the largest v0 component of the triangle records
+    double E = 0.0, V = 0.0;
+    for (uint32_t i = 0; i < L.tris; ++i) {
+        const float *r = &L.prims[12 * (size_t)i];
+        for (int k = 0; k < 3; ++k) {
+            if (!std::isfinite(r[k]) || !std::isfinite(r[4 + k]) || !std::isfinite(r[8 + k])) return 0.0f;
+            V = std::max(V, std::fabs((double)r[k]));
+            E = std::max({E, std::fabs((double)r[4 + k]), std::fabs((double)r[8 + k])});
+        }
+    }
+    // |o_i|, |d_i| <= M.  In magnitude, per component: tvec = o - v0 <= M + V;
+    // pvec = d x e2 <= 2 M E; qvec = tvec x e1 <= 2 (M + V) E; and the dots
+    // det = e1 . pvec, tvec . pvec, d . qvec, e2 . qvec three such products
+    // each; d . d <= 3 M^2.  Every partial sum obeys the same bound, and the
+    // roundings of at most five operations are inside the factor `slack`.
+    const double lim = std::ldexp(1.0, 125), slack = 1.0 + std::ldexp(1.0, -20);
+    auto fits = [&](double M) {
+        const double tv = M + V, pv = 2.0 * M * E, qv = 2.0 * tv * E;
+        const double worst = std::max({tv, pv, qv, 3.0 * E * pv, 3.0 * tv * pv, 3.0 * M * qv, 3.0 * E * qv, 6.0 * M * M});
+        return worst * slack <= lim;
+    };
+    double M = std::ldexp(1.0, 60);
+    while (M >= 1.0 && !fits(M)) M *= 0.5;
+    if (M < 1.0 || M < 16.0 * std::max(V, E)) return 0.0f;
+    return (float)M;
+}
 ScanList build_scan_list(const DeviceBvh &bvh, uint32_t n) {
+    ScanList L = build_scan_list_(bvh, n);
+    L.fast_max = scan_fast_max(L);
+    return L;
+}
+static ScanList build_scan_list_(const DeviceBvh &bvh, uint32_t n) {
     ScanList L;
     auto rec = [&](uint32_t i) { return &bvh.prims[12 * (size_t)i]; };
     auto sphere = [&](uint32_t i) {
@@ -503,6 +537,19 @@ int nori_scene_scan_list(const nori_scene_desc *d, nori_scan_info *info, float *
         if (records) std::memcpy(records, L.prims.data(), L.prims.size() * 4);
         if (plane_c && !L.plane_c.empty()) std::memcpy(plane_c, L.plane_c.data(), L.plane_c.size() * 4);
         if (plane_f && !L.plane_f.empty()) std::memcpy(plane_f, L.plane_f.data(), L.plane_f.size() * 4);
+        return NORI_OK;
+    });
+}
+int nori_scene_scan_fast(const nori_scene_desc *d, float *fast_max) {
+    return guarded([&] {
+        if (!d || !fast_max) return fail(NORI_ERR_INVALID, "null argument");
+        if (d->abi_version != NORI_GPU_ABI_VERSION) return fail(NORI_ERR_INVALID, "ABI version mismatch");
+        float rmin[3], rmax[3];
+        scene_root_box(*d, rmin, rmax);
+        DeviceBvh bvh;
+        build_device_bvh(*d, rmin, rmax, bvh);
+        const uint32_t n = (uint32_t)(bvh.prims.size() / 12);
+        *fast_max = n > kScanMaxPrims ? 0.0f : build_scan_list(bvh, n).fast_max;
         return NORI_OK;
     });
 }

@@ -87,8 +87,18 @@ struct ScanList {
     uint32_t plane_end[3] = {0, 0, 0};  // pairs with axis <= a
     uint32_t tris = 0;          // triangle records (pairs + the rest, padded)
     uint32_t real = 0;          // ... of which the last real one ends here (the padding after it never hits)
+    float fast_max = 0.0f;      // scan_fast_max of this list
 };
 ScanList build_scan_list(const DeviceBvh &bvh, uint32_t n);
+// The bound M of the scene-specialised scan's fast body (scan.h): a ray whose
+// origin and direction components are all at most M in magnitude keeps every
+// intermediate of the triangle tests of this list -- tvec, pvec, qvec, det and
+// the numerators of u, v and t -- and the sphere test's 2 d.d at or below
+// 2^125, so none overflows and det lies in rcp_rn's verified range.  M is the
+// largest power of two up to 2^60 for which the bounds below hold; a list
+// whose coordinates leave no room for rays around it (M < 16 times its largest
+// coordinate or edge) gets 0, no fast body.  NORI_SCAN_FAST=0 gives 0 as well (A/B).
+float scan_fast_max(const ScanList &L);
 
 // The path kernels' lite variants (FULL = false) serve scenes made of the
 // basic plugins only: constant-albedo diffuse, mirror and dielectric BSDFs,

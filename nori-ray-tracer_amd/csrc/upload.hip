@@ -63,7 +63,8 @@ bool shade_rtc_scene(const nori_scene_desc &d, bool scan, size_t records) {
 
 ScanRtcScene rtc_scene_of(const ScanList &L) {
     return ScanRtcScene{L.prims.data(), (uint32_t)(L.prims.size() / 12), L.plane_c.data(), L.plane_f.data(),
-                        (uint32_t)L.plane_c.size(), {L.plane_end[0], L.plane_end[1], L.plane_end[2]}, L.tris, L.real};
+                        (uint32_t)L.plane_c.size(), {L.plane_end[0], L.plane_end[1], L.plane_end[2]}, L.tris, L.real,
+                        L.fast_max};
 }
 
 void upload_scene(nori_gpu_ctx &c, const nori_scene_desc &d) {

@@ -393,6 +393,15 @@ def scan_list(scene):
             "plane_end": np.array(list(info.plane_end)), "tris": info.tris}
 
 
+def scan_fast_max(scene):
+    """The bound of the fast body in the scene's specialised scan and shade programs
+    (nori_scene_scan_fast): a wave whose rays all have sum(|o|) + sum(|d|) at or below it takes
+    that body; 0.0 when the programs are built without one."""
+    m = C.c_float()
+    check(lib().nori_scene_scan_fast(scene.desc_ptr, C.byref(m)))
+    return m.value
+
+
 def scan_rtc(scene, arch="gfx950"):
     """Compile the scene's scan kernels specialised for its scan list for `arch` (the hipRTC program
     GpuRenderer loads for scan-mode scenes; no device needed): (code object bytes, milliseconds);

@@ -203,6 +203,7 @@ SIGNATURES = {
     "nori_scene_bvh_info": (C.c_int, [C.c_void_p, C.c_void_p]),
     "nori_scene_scan_list": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float),
                                        C.POINTER(C.c_float)]),
+    "nori_scene_scan_fast": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "nori_scene_scan_rtc": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_size_t), C.POINTER(C.c_double)]),
     "nori_scene_shade_rtc": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_size_t), C.POINTER(C.c_double)]),
     "nori_gpu_shade_rtc_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double),
@@ -265,7 +266,7 @@ ADDED_IN_7 = {"nori_gpu_query", "nori_scene_surface", "nori_gpu_camera_rays", "n
               "nori_gpu_bvh_read", "nori_scene_bvh_refit", "nori_scene_bvh_rebuild", "nori_gpu_rebuild_bvh",
               "nori_scene_shade_rtc", "nori_gpu_shade_rtc_info", "nori_gpu_bsdf_eval", "nori_gpu_bsdf_sample",
               "nori_gpu_emitter_sample", "nori_gpu_emitter_eval", "nori_gpu_sample_uniforms", "nori_film_splat",
-              "nori_gpu_film_splat", "nori_gpu_film_splat_passes"}
+              "nori_gpu_film_splat", "nori_gpu_film_splat_passes", "nori_scene_scan_fast"}
 
 COMM_ID_BYTES = 128
 SHARD_PASSES, SHARD_BLOCKS = 0, 1
