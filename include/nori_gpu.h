@@ -23,6 +23,10 @@
  *                            (nori_scene_surface: the same record on the host)
  *   nori_gpu_camera_rays  <- Camera::sampleRay src/perspective.cpp:90-112,
  *                            src/thinlens.cpp:120-147, src/advancedCamera.cpp:85-157
+ *   nori_gpu_li           <- Integrator::Li include/nori/integrator.h:55 (a batch of
+ *                            the caller's rays; src/path_mis.cpp, path_mats.cpp,
+ *                            volumetric.cpp, direct*.cpp, normals.cpp,
+ *                            averagevisibility.cpp, photonmapper.cpp)
  *   nori_gpu_cancel       <- RenderThread::stopRendering  src/render.cpp:63-71
  *   nori_gpu_progress     <- RenderThread::getProgress    src/render.cpp:73-78
  *   nori_film_develop     <- ImageBlock::toBitmap         src/block.cpp:76-82
@@ -770,6 +774,78 @@ int nori_gpu_emitter_eval(nori_gpu_ctx *ctx, const nori_gpu_shading_desc *desc, 
  * stream. */
 int nori_gpu_sample_uniforms(nori_gpu_ctx *ctx, const nori_gpu_render_desc *desc, uint32_t first,
                              uint32_t count, float *out);
+
+/* ---- radiance queries: Integrator::Li along the caller's rays ----
+ * (the reference calls Li(scene, sampler, ray) one ray at a time,
+ * include/nori/integrator.h:55; the batch form, its stream convention and its
+ * chromatic rule are deviation D18)
+ * The built-in integrators without the scene's camera, pixel grid and film:
+ *   nori_gpu_camera_rays or your own rays -> nori_gpu_li -> nori_gpu_film_splat */
+typedef struct nori_gpu_li_desc {
+    uint32_t n;            /* rays */
+    int32_t  on_device;    /* rays, stream_ids and out are device memory on the context's device */
+    uint64_t seed;         /* as nori_gpu_render_desc.seed */
+    uint64_t stream_base;  /* stream_ids == NULL: ray i draws from wave_seed(seed, stream_base + i) */
+    uint32_t first_draw;   /* draws of that stream skipped before the integrator's first (<= 65535) */
+    uint32_t reserved;     /* must be 0 */
+} nori_gpu_li_desc;        /* 32 bytes */
+/* Arrays.  rays: n x 8 floats (o.xyz, mint, d.xyz, maxt), 16-byte aligned on
+ * the device, as for nori_gpu_query.  stream_ids: NULL, or n x uint64 (8-byte
+ * aligned on the device): ray i then draws from wave_seed(seed, stream_ids[i]),
+ * so that rays the caller has compacted or permuted keep their streams.  out:
+ * n x 3 floats, packed (4-byte aligned on the device) -- the `val` layout of
+ * nori_gpu_film_splat, which it feeds without a copy.
+ * What is computed.  out[i] = Integrator::Li(scene, sampler, Ray3f(o, d, mint,
+ * maxt)) of the context's integrator -- any of path_mis, path_mats, volumetric,
+ * normals, av, direct, direct_ems, direct_mats, direct_mis, photonmapper -- with
+ * the sampler being the pcg32 stream above after first_draw calls of next1D.
+ * The first segment uses the ray's own mint and maxt, every later segment
+ * (NORI_EPSILON, +inf) as in the renderer; d is used as given, not normalised.
+ * The value is the one the render kernels compute for a camera sample that
+ * starts with this ray: the same routines, the same order of the draws
+ * (nori_gpu_sample_uniforms lists it) and the same order of the additions,
+ * which start from +0 and add, per path vertex, the emission first and then
+ * the next-event term if its shadow ray is unoccluded.  The result of a ray
+ * depends on its eight floats, its stream and first_draw only -- not on n, on
+ * its place in the batch, or on NORI_LI_RANGE / NORI_LI_REFILL below.
+ * The renderer's samples.  For a camera without chromatic aberration, take the
+ * rays of nori_gpu_camera_rays(pass_begin = p, pass_count = k, seed = s) as
+ * k H W rows and call nori_gpu_li with seed = s, stream_base = p W H and
+ * first_draw = 4 (draws 0..3 are the pixel jitter and the aperture sample):
+ * out holds exactly the radiance of the samples nori_gpu_render takes for
+ * those passes -- the values its variance_out statistics add to +0.  A
+ * chromatic sample cannot be reproduced this way: the renderer calls Li three
+ * times on one stream, once per channel's ray, and keeps one channel of each.
+ * Chromatic aberration is a property of the camera, and Li knows no camera:
+ * nori_gpu_li returns all three channels of every ray, also on a context whose
+ * camera has chromaticAberation set.
+ * Invalid values.  A value that is negative or not finite is written as
+ * computed (nori_gpu_film_splat drops and counts it, as block.cpp:94-98 does)
+ * and its row is counted in stats->invalid_samples.  A ray is not traced, and
+ * its row is three zeros (a valid value), when a component of o or d, or mint,
+ * is not finite, when maxt is NaN, or when d is zero: nori_gpu_camera_rays
+ * leaves the entries of unselected blocks untouched, so all-zero rays are an
+ * expected input.  (A ray with maxt < mint is traced and hits nothing.)
+ * NORI_ERR_INVALID, nothing launched, the context stays usable: a null ctx,
+ * desc, rays or out; reserved != 0; first_draw > 65535; on_device with a
+ * pointer that is misaligned or that the HIP runtime does not know as device
+ * memory.  n == 0 is a no-op.
+ * Host arrays are staged through context-owned buffers in chunks of at most
+ * NORI_QUERY_CHUNK rays; device arrays are used in place, nothing is allocated
+ * per call, and the caller has made them ready before the call.  Blocking; runs
+ * on the context's stream in launches of at most 16M rays, between which
+ * nori_gpu_cancel is honoured (NORI_ERR_CANCELLED; a host `out` is left
+ * unchanged then, a device `out` holds the launches that ran) and over which
+ * nori_gpu_progress rises.  After nori_gpu_update_vertices /
+ * nori_gpu_rebuild_bvh it answers for the geometry as it is now.
+ * stats (may be NULL): samples = n, invalid_samples, rays_closest, rays_shadow,
+ * ms_total (wall time), ms_shade = HIP-event time of the kernel.
+ * Environment, read at every call: NORI_LI_RANGE (64 .. 4096, default 256) --
+ * the consecutive rays one wave owns; a lane whose path has ended starts the
+ * next ray of its wave's range; NORI_LI_REFILL=0 -- every lane takes exactly
+ * one ray instead (the A/B of that refill). */
+int nori_gpu_li(nori_gpu_ctx *ctx, const nori_gpu_li_desc *desc, const float *rays,
+                const uint64_t *stream_ids, float *out, nori_gpu_stats *stats);
 
 /* ---- film splat: caller-supplied samples filtered into the film ----
  * (no reference counterpart as an API: it is ImageBlock::put(pos, value)

@@ -1,7 +1,7 @@
 // ctx.h -- the runtime units' private view of a context: nori_gpu_ctx and
 // nori_gpu_comm, device buffers, HIP error handling, and the few functions
 // that cross units.  Included by upload.hip, render.hip, queries.hip,
-// film_splat.hip, adaptive.hip, dynamic.hip and sharded.hip only.
+// film_splat.hip, li.hip, adaptive.hip, dynamic.hip and sharded.hip only.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -115,6 +115,8 @@ struct nori_gpu_ctx {
     // the shading queries (nori_gpu_bsdf_eval ..): staging of up to three host input arrays and the output
     // (nori_gpu_film_splat*: sh_in[0] / sh_in[1] stage host positions and values, q_ev[0..1] time the kernels)
     DevBuf sh_in[3], sh_out;
+    // nori_gpu_li: its ray and invalid-row counters (rays, stream ids and values are staged in q_rays, sh_in[0], sh_out)
+    DevBuf li_count;
     DevBuf ph, ph_rgbe, ph_tab, ph_start;             // photonmapper: photon map (photon_map.cpp) and its hash-grid buckets
     // nori_gpu_update_vertices: the refit schedule (host copy of its level bounds, device copy of
     // its slots), staging of host positions / normals, the non-finite counter, the shapes as

@@ -4,8 +4,8 @@
 // in kernels_features.hip; launch_surface and launch_camera_rays in
 // kernels_query.hip; the shading queries in kernels_shading.hip; the
 // denoisers, the block error and the refit in denoise.hip, block_error.hip
-// and refit.hip; the caller-fed film splats in kernels_film.hip; all others in
-// kernels.hip.
+// and refit.hip; the caller-fed film splats in kernels_film.hip; launch_li in
+// kernels_li.hip; all others in kernels.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -196,6 +196,23 @@ hipError_t launch_emitter_eval(const DevScene &S, uint32_t num_shapes, const flo
 hipError_t launch_sample_uniforms(const DevScene &S, const uint32_t *pixels, uint32_t M, uint32_t pass_begin,
                                   uint32_t k0, uint32_t np, uint64_t seed, uint32_t first, uint32_t count, float *out,
                                   hipStream_t st);
+// Radiance queries (kernels_li.hip k_li; stated at nori_gpu_li in nori_gpu.h):
+// Li of the context's integrator along row i < n of `rays` (two float4, 16-byte
+// aligned) on the stream wave_seed(seed, ids ? ids[i] : stream_base + i) after
+// first_draw draws, written at out[3 i]; all device memory.  A wave owns
+// `range` (>= 64) consecutive rows; refill != 0: a lane whose path has ended
+// starts the next row of its wave's range (0: one row per lane, range 64).
+// counters[0..2] += closest-hit rays, shadow rays, rows whose value fails
+// Color3f::isValid.
+struct LiArgs {
+    const float4 *rays;
+    const uint64_t *ids;  // or null
+    float *out;
+    uint32_t n, range, refill, first_draw;
+    uint64_t seed, stream_base;
+    unsigned long long *counters;
+};
+hipError_t launch_li(const DevScene &S, const LiArgs &a, int stack, hipStream_t st);
 hipError_t launch_splat(const DevScene &S, const float4 *rec, const SplatDesc &sd, uint32_t nblocks, float *film,
                         Counters *C, hipStream_t st);
 // Caller-supplied samples into the film (kernels_film.hip; stated at

@@ -776,6 +776,51 @@ class GpuRenderer:
         check(lib().nori_gpu_sample_uniforms(self._h, C.byref(rd), int(first), int(count), C.c_void_p(out.ctypes.data)))
         return out
 
+    def li(self, rays, stream_ids=None, seed=0, stream_base=0, first_draw=0, n=None, out=None):
+        """Integrator::Li of the context's integrator along the caller's rays (nori_gpu_li, stated in
+        nori_gpu.h): ray i draws from the stream wave_seed(seed, stream_ids[i]) -- stream_base + i
+        when stream_ids is None -- after `first_draw` draws.  With the rays of camera_rays(passes=k,
+        pass_begin=p, seed=s) as rows, seed=s, stream_base=p * W * H and first_draw=4 give the
+        radiance of the samples render() takes for those passes.
+        Host form: `rays` (n, 8) float32 (o.xyz, mint, d.xyz, maxt), `stream_ids` None or n uint64;
+        returns (n, 3) float32 (written into `out` when given).  Device form: int device addresses
+        or torch tensors on the context's device with n= and out= (n x 3 floats; rays 16-byte,
+        stream_ids 8-byte aligned): used in place, None is returned, and the buffers must be ready
+        before the call.  last_stats: samples, invalid_samples, rays_closest, rays_shadow, ms_shade."""
+        ld = _abi.LiDesc(0, 0, int(seed), int(stream_base), int(first_draw), 0)
+        st = _abi.Stats()
+
+        def addr(a):
+            return None if a is None else C.c_void_p(int(a.data_ptr() if hasattr(a, "data_ptr") else a))
+        if not isinstance(rays, np.ndarray):
+            if isinstance(stream_ids, np.ndarray) or isinstance(out, np.ndarray):
+                raise ValueError("li: the arrays must all be numpy arrays or all be device addresses")
+            if n is None or out is None:
+                raise ValueError("li: device addresses need n= and a device address out=")
+            ld.n, ld.on_device = int(n), 1
+            check(lib().nori_gpu_li(self._h, C.byref(ld), addr(rays), addr(stream_ids), addr(out), C.byref(st)))
+            self.last_stats = st.as_dict()
+            return None
+        rays = np.ascontiguousarray(rays, dtype=np.float32)
+        if rays.ndim != 2 or rays.shape[1] != 8:
+            raise ValueError(f"rays {rays.shape}: expected (n, 8)")
+        ld.n = rays.shape[0]
+        if n is not None and int(n) != ld.n:
+            raise ValueError(f"li: {ld.n} rays, expected {int(n)}")
+        ids = None
+        if stream_ids is not None:
+            ids = np.ascontiguousarray(stream_ids, dtype=np.uint64).reshape(-1)
+            if ids.shape[0] != ld.n:
+                raise ValueError(f"li: {ids.shape[0]} stream ids for {ld.n} rays")
+        if out is None:
+            out = np.zeros((ld.n, 3), np.float32)
+        assert isinstance(out, np.ndarray) and out.dtype == np.float32 and out.flags.c_contiguous and out.shape == (ld.n, 3)
+        check(lib().nori_gpu_li(self._h, C.byref(ld), C.c_void_p(rays.ctypes.data),
+                                None if ids is None else C.c_void_p(ids.ctypes.data), C.c_void_p(out.ctypes.data),
+                                C.byref(st)))
+        self.last_stats = st.as_dict()
+        return out
+
     def _splat_args(self, name, pos, val, n, out, variance):
         """(on_device, n, pos, val, film, variance addresses, the film to return) of a film splat:
         all numpy (host form) or all device addresses / torch tensors with a device film out=."""
