@@ -49,7 +49,7 @@ int render_adaptive(nori_gpu_ctx &c, const nori_gpu_render_desc &rd0, const nori
     if (!(ad.threshold >= 0.0f)) throw NoriException(NORI_ERR_INVALID, "adaptive: threshold is negative or NaN");
     if (ad.reserved != 0) throw NoriException(NORI_ERR_INVALID, "adaptive: reserved must be 0");
     if ((uint64_t)rd0.pass_begin + cap > 0xFFFFFFFFull) throw NoriException(NORI_ERR_INVALID, "adaptive: pass range overflows");
-    const int W = c.S.W, H = c.S.H, B = c.S.border;
+    const int W = c.S.W, H = c.S.H;
     int nbx = 0;
     const uint32_t nb = (uint32_t)frame_blocks(c, &nbx);
     // the selected blocks, ascending, duplicates dropped
@@ -77,13 +77,10 @@ int render_adaptive(nori_gpu_ctx &c, const nori_gpu_render_desc &rd0, const nori
     };
     const double bound = (double)cap * (double)pixels_of(active);  // samples if no block stops early
 
-    const size_t film_elems = 4 * (size_t)(W + 2 * B) * (H + 2 * B), var_elems = 8 * (size_t)W * (size_t)H;
-    float *film = rgbw_out;
-    if (!rd0.output_on_device) {
-        c.film.ensure(film_elems * sizeof(float));
-        film = c.film.as<float>();
-        HIP_TRY(hipMemsetAsync(film, 0, film_elems * sizeof(float), c.stream));
-    }
+    // (the statistics are always gathered, in c.varbuf: the rounds' errors are read from them)
+    const size_t var_elems = 8 * (size_t)W * (size_t)H;
+    FilmOut out(c, rd0.output_on_device != 0, rgbw_out);
+    out.begin();
     c.varbuf.ensure(var_elems * sizeof(float));
     c.errbuf.ensure((size_t)nb * sizeof(float));
     c.errids.ensure((size_t)nb * sizeof(uint32_t));
@@ -122,7 +119,7 @@ int render_adaptive(nori_gpu_ctx &c, const nori_gpu_render_desc &rd0, const nori
         rd.block_ids = active.data();
         rd.output_on_device = 1;
         rd.variance_out = c.varbuf.as<float>();
-        const int rc = render(c, rd, film, &rs);
+        const int rc = render(c, rd, out.film, &rs);
         if (rc != NORI_OK) return rc;
         sum.samples += rs.samples;
         sum.invalid_samples += rs.invalid_samples;
@@ -152,15 +149,12 @@ int render_adaptive(nori_gpu_ctx &c, const nori_gpu_render_desc &rd0, const nori
     }
     if (c.cancel.load()) return fail(NORI_ERR_CANCELLED, "rendering was cancelled");
 
-    if (!rd0.output_on_device) {
-        std::vector<float> hf(std::max(film_elems, var_elems));
-        HIP_TRY(hipMemcpy(hf.data(), film, film_elems * sizeof(float), hipMemcpyDeviceToHost));
-        for (size_t i = 0; i < film_elems; ++i) rgbw_out[i] += hf[i];
-        if (rd0.variance_out) {
-            HIP_TRY(hipMemcpy(hf.data(), c.varbuf.p, var_elems * sizeof(float), hipMemcpyDeviceToHost));
-            for (size_t i = 0; i < var_elems; ++i) rd0.variance_out[i] += hf[i];
-        }
-    } else if (rd0.variance_out) {
+    out.finish(false);
+    if (!rd0.output_on_device && rd0.variance_out) {
+        std::vector<float> hv(var_elems);
+        HIP_TRY(hipMemcpy(hv.data(), c.varbuf.p, var_elems * sizeof(float), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < var_elems; ++i) rd0.variance_out[i] += hv[i];
+    } else if (rd0.output_on_device && rd0.variance_out) {
         HIP_TRY(launch_add_into(rd0.variance_out, c.varbuf.as<float>(), var_elems, c.stream));
         HIP_TRY(hipStreamSynchronize(c.stream));
     }

@@ -1,10 +1,11 @@
 // ctx.h -- the runtime units' private view of a context: nori_gpu_ctx and
-// nori_gpu_comm, device buffers, HIP error handling, and the few functions
-// that cross units.  Included by upload.hip, render.hip, queries.hip,
+// nori_gpu_comm, device buffers, HIP error handling, the kernel clock, the
+// film target, and the few functions that cross units.  Included by upload.hip, render.hip, queries.hip,
 // film_splat.hip, li.hip, adaptive.hip, dynamic.hip and sharded.hip only.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <cstring>
@@ -13,6 +14,7 @@
 
 #include "comm.h"
 #include "kernels.h"
+#include "render_plan.h"
 #include "scene_prep.h"
 
 #define HIP_TRY(x)                                                                                       \
@@ -51,23 +53,64 @@ struct DevBuf {
     template <class T> T *as() const { return reinterpret_cast<T *>(p); }
 };
 
-struct Timers {
+enum KernelKind { kKindExtend, kKindShadow, kKindShade, kKindSplat, kKindFinish, kKernelKinds };  // the ms_* of nori_gpu_stats
+
+// The HIP-event times of a call's launches, summed per kind.  A local clock per
+// timed render; the context's own (c.clock) for the queries, which collect after
+// every chunk and so reuse the same three events.
+struct KernelClock {
+    struct Span {
+        size_t a, b;  // indices into ev
+        int kind;
+    };
+    bool on;
+    double ms[kKernelKinds] = {};
     std::vector<hipEvent_t> ev;
     size_t used = 0;
-    hipEvent_t get() {
+    std::vector<Span> spans;  // not yet collected
+    explicit KernelClock(bool enabled = true) : on(enabled) {}
+    KernelClock(const KernelClock &) = delete;
+    ~KernelClock() {
+        for (auto e : ev) (void)hipEventDestroy(e);
+    }
+    void reset(bool enabled) {  // (the context's clock, at the start of a call)
+        on = enabled;
+        spans.clear();
+        used = 0;
+        std::memset(ms, 0, sizeof(ms));
+    }
+    size_t mark(hipStream_t st) {
         if (used == ev.size()) {
             hipEvent_t e;
             HIP_TRY(hipEventCreate(&e));
             ev.push_back(e);
         }
-        return ev[used++];
+        HIP_TRY(hipEventRecord(ev[used], st));
+        return used++;
     }
-    ~Timers() {
-        for (auto e : ev) (void)hipEventDestroy(e);
+    // launch() on `st`, between two events when the clock is enabled.  chained: the
+    // launch follows the last span's on the same stream with nothing between, and
+    // that span's end event is this one's start.
+    template <class Launch> void span(hipStream_t st, int kind, Launch &&launch, bool chained = false) {
+        if (!on) {
+            HIP_TRY(launch());
+            return;
+        }
+        const size_t a = chained && !spans.empty() ? spans.back().b : mark(st);
+        HIP_TRY(launch());
+        spans.push_back(Span{a, mark(st), kind});
+    }
+    // after the caller has synchronised the spans' streams: their times into ms[], the events free again
+    void collect() {
+        for (const Span &s : spans) {
+            float t = 0.0f;
+            HIP_TRY(hipEventElapsedTime(&t, ev[s.a], ev[s.b]));
+            ms[s.kind] += t;
+        }
+        spans.clear();
+        used = 0;
     }
 };
-
-constexpr int kMaxParts = 4;  // pool parts on separate streams (GPU_MAX_HW_QUEUES is 4)
 
 }  // namespace nori
 
@@ -109,11 +152,12 @@ struct nori_gpu_ctx {
     DevBuf q[2][5], sq[3], seg[4], segstats, tailpre, rec, counters, pixels, blocks, film;
     DevBuf varbuf;                   // per-pixel sample statistics when variance_out is a host buffer
     // nori_gpu_query / nori_gpu_camera_rays: staging of host rays, hits and records (q_hits also
-    // serves a device query without a hit output), reused across calls; events around the two kernels
+    // serves a device query without a hit output), reused across calls; the clock of their kernels
+    // (and of nori_gpu_li's and the film splats')
     DevBuf q_rays, q_hits, q_surf;
-    hipEvent_t q_ev[3] = {};
+    KernelClock clock;
     // the shading queries (nori_gpu_bsdf_eval ..): staging of up to three host input arrays and the output
-    // (nori_gpu_film_splat*: sh_in[0] / sh_in[1] stage host positions and values, q_ev[0..1] time the kernels)
+    // (nori_gpu_film_splat*: sh_in[0] / sh_in[1] stage host positions and values)
     DevBuf sh_in[3], sh_out;
     // nori_gpu_li: its ray and invalid-row counters (rays, stream ids and values are staged in q_rays, sh_in[0], sh_out)
     DevBuf li_count;
@@ -160,8 +204,6 @@ struct nori_gpu_ctx {
         }
         scan_rtc_release(rtc);
         shade_rtc_release(shade_rtc);
-        for (auto e : q_ev)
-            if (e) (void)hipEventDestroy(e);
         for (auto e : upd_ev)
             if (e) (void)hipEventDestroy(e);
         for (auto e : rb_ev)
@@ -211,9 +253,53 @@ inline void scene_stats(const nori_gpu_ctx &c, std::chrono::steady_clock::time_p
     s->ms_scan_rtc = c.rtc.compile_ms;
 }
 
+// The start of a call's statistics (stats may be null: false): zeroed, scene_stats, one stream.
+inline bool begin_stats(const nori_gpu_ctx &c, std::chrono::steady_clock::time_point t0, nori_gpu_stats *s) {
+    if (!s) return false;
+    std::memset(s, 0, sizeof(*s));
+    scene_stats(c, t0, s);
+    s->stream_parts = 1;
+    return true;
+}
+
+// Where a call's kernels add the film and the per-pixel sample statistics: the
+// caller's own arrays when they are device memory, else zeroed context buffers
+// (c.film, c.varbuf) that finish() adds into the caller's host arrays.
+struct FilmOut {
+    nori_gpu_ctx &c;
+    const bool on_device;
+    float *const rgbw, *const variance;  // the caller's (variance may be null)
+    float *film = nullptr, *var = nullptr;  // the device pointers, set by begin()
+    const size_t film_elems, var_elems;
+    FilmOut(nori_gpu_ctx &ctx, bool dev, float *rgbw_, float *variance_ = nullptr)
+        : c(ctx), on_device(dev), rgbw(rgbw_), variance(variance_),
+          film_elems(4 * (size_t)(c.S.W + 2 * c.S.border) * (size_t)(c.S.H + 2 * c.S.border)),
+          var_elems(8 * (size_t)c.S.W * (size_t)c.S.H) {}
+    void begin() {
+        film = rgbw;
+        var = variance;
+        if (on_device) return;
+        c.film.ensure(film_elems * sizeof(float));
+        film = c.film.as<float>();
+        HIP_TRY(hipMemsetAsync(film, 0, film_elems * sizeof(float), c.stream));
+        if (!variance) return;
+        c.varbuf.ensure(var_elems * sizeof(float));
+        var = c.varbuf.as<float>();
+        HIP_TRY(hipMemsetAsync(var, 0, var_elems * sizeof(float), c.stream));
+    }
+    void finish(bool cancelled) {  // (a cancelled call leaves the host arrays as they were)
+        if (on_device || cancelled) return;
+        std::vector<float> h(variance ? std::max(film_elems, var_elems) : film_elems);
+        HIP_TRY(hipMemcpy(h.data(), film, film_elems * sizeof(float), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < film_elems; ++i) rgbw[i] += h[i];
+        if (!variance) return;
+        HIP_TRY(hipMemcpy(h.data(), var, var_elems * sizeof(float), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < var_elems; ++i) variance[i] += h[i];
+    }
+};
+
 int bvh_stack_for(uint32_t depth, int forced);                                                         // upload.hip
 void work_lists(nori_gpu_ctx &c, const nori_gpu_render_desc &rd);                                       // render.hip
 int render(nori_gpu_ctx &c, const nori_gpu_render_desc &rd, float *rgbw_out, nori_gpu_stats *stats);   // render.hip
-uint32_t query_chunk();  // queries.hip: NORI_QUERY_CHUNK, the most elements of a host array staged at once
 
 }  // namespace nori

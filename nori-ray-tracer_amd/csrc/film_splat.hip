@@ -30,85 +30,45 @@ void check_device_array(const char *name, const char *what, const void *p, size_
     require_device_ptr(p, std::string(name) + ": " + what + " is not device memory");
 }
 
-// Where a call's kernels add: the caller's device film and statistics, or
-// zeroed context buffers that finish() adds into the host arrays; the dropped
-// samples' counter; the HIP-event time of the kernels.
+// A splat call's target: the checked film and statistics (ctx.h FilmOut), the
+// dropped samples' counter and the HIP-event time of the kernels (c.clock).
 struct FilmTarget {
     nori_gpu_ctx &c;
-    const bool on_device;
-    float *const rgbw, *const variance;
-    float *film = nullptr, *var = nullptr;
+    FilmOut out;
     unsigned long long *dropped = nullptr;
-    size_t film_elems = 0, var_elems = 0;
-    double ms = 0.0;
-    FilmTarget(nori_gpu_ctx &ctx, const char *name, bool dev, float *rgbw_, float *variance_)
-        : c(ctx), on_device(dev), rgbw(rgbw_), variance(variance_) {
-        const size_t W = (size_t)c.S.W, H = (size_t)c.S.H, B = (size_t)c.S.border;
+    FilmTarget(nori_gpu_ctx &ctx, const char *name, bool dev, float *rgbw, float *variance)
+        : c(ctx), out(ctx, dev, rgbw, variance) {
         if (c.S.border > 4) throw NoriException(NORI_ERR_HIP, std::string(name) + ": filter radius above 4.5 pixels");
-        film_elems = 4 * (W + 2 * B) * (H + 2 * B);
-        var_elems = 8 * W * H;
-        if (on_device) {
+        if (dev) {
             check_device_array(name, "rgbw", rgbw, 16);
             if (variance) check_device_array(name, "variance_out", variance, 16);
         }
     }
     void begin() {  // (after every check of the call: nothing is launched before)
-        if (on_device) {
-            film = rgbw;
-            var = variance;
-        } else {
-            c.film.ensure(film_elems * sizeof(float));
-            film = c.film.as<float>();
-            HIP_TRY(hipMemsetAsync(film, 0, film_elems * sizeof(float), c.stream));
-            if (variance) {
-                c.varbuf.ensure(var_elems * sizeof(float));
-                var = c.varbuf.as<float>();
-                HIP_TRY(hipMemsetAsync(var, 0, var_elems * sizeof(float), c.stream));
-            }
-        }
+        out.begin();
         c.counters.ensure(sizeof(Counters));
         HIP_TRY(hipMemsetAsync(c.counters.p, 0, sizeof(Counters), c.stream));
         dropped = &c.counters.as<Counters>()->invalid;
-        for (int k = 0; k < 2; ++k)
-            if (!c.q_ev[k]) HIP_TRY(hipEventCreate(&c.q_ev[k]));
+        c.clock.reset(true);
     }
     // One kernel launch, timed; the stream has drained when it returns (so the
     // staging buffers it read may be refilled).
     template <class Launch> void run(Launch &&launch) {
-        HIP_TRY(hipEventRecord(c.q_ev[0], c.stream));
-        HIP_TRY(launch());
-        HIP_TRY(hipEventRecord(c.q_ev[1], c.stream));
+        c.clock.span(c.stream, kKindSplat, launch);
         HIP_TRY(hipStreamSynchronize(c.stream));
-        float a = 0.0f;
-        HIP_TRY(hipEventElapsedTime(&a, c.q_ev[0], c.q_ev[1]));
-        ms += a;
+        c.clock.collect();
     }
-    uint64_t finish() {  // returns the dropped samples
+    // The call's statistics; the film and the variance into a host caller's arrays.
+    void finish(std::chrono::steady_clock::time_point t0, uint64_t total, nori_gpu_stats *stats) {
         unsigned long long d = 0;
         HIP_TRY(hipMemcpy(&d, dropped, sizeof(d), hipMemcpyDeviceToHost));
-        if (!on_device) {
-            std::vector<float> h(std::max(film_elems, var_elems));
-            HIP_TRY(hipMemcpy(h.data(), film, film_elems * sizeof(float), hipMemcpyDeviceToHost));
-            for (size_t i = 0; i < film_elems; ++i) rgbw[i] += h[i];
-            if (variance) {
-                HIP_TRY(hipMemcpy(h.data(), var, var_elems * sizeof(float), hipMemcpyDeviceToHost));
-                for (size_t i = 0; i < var_elems; ++i) variance[i] += h[i];
-            }
-        }
-        return d;
+        out.finish(false);
+        if (!begin_stats(c, t0, stats)) return;
+        stats->samples = total - d;
+        stats->invalid_samples = d;
+        stats->ms_splat = c.clock.ms[kKindSplat];
     }
 };
-
-void splat_stats(const nori_gpu_ctx &c, std::chrono::steady_clock::time_point t0, uint64_t total, uint64_t dropped,
-                 double ms, nori_gpu_stats *stats) {
-    if (!stats) return;
-    std::memset(stats, 0, sizeof(*stats));
-    scene_stats(c, t0, stats);
-    stats->samples = total - dropped;
-    stats->invalid_samples = dropped;
-    stats->stream_parts = 1;
-    stats->ms_splat = ms;
-}
 
 int film_splat(nori_gpu_ctx &c, const nori_gpu_splat_desc &sd, const float *pos, const float *val, float *rgbw,
                nori_gpu_stats *stats) {
@@ -123,9 +83,11 @@ int film_splat(nori_gpu_ctx &c, const nori_gpu_splat_desc &sd, const float *pos,
     const FilmGeom F = film_geom(c);
     T.begin();
     if (sd.on_device) {
-        T.run([&] { return launch_splat_scatter(F, sd.n, kScatterRows, pos, val, T.film, T.var, T.dropped, c.stream); });
+        T.run([&] {
+            return launch_splat_scatter(F, sd.n, kScatterRows, pos, val, T.out.film, T.out.var, T.dropped, c.stream);
+        });
     } else {
-        const uint64_t chunk = std::min<uint64_t>(sd.n, query_chunk());
+        const uint64_t chunk = std::min<uint64_t>(sd.n, query_chunk(std::getenv("NORI_QUERY_CHUNK")));
         c.sh_in[0].ensure(8 * (size_t)chunk);
         c.sh_in[1].ensure(12 * (size_t)chunk);
         for (uint64_t i0 = 0; i0 < sd.n; i0 += chunk) {
@@ -133,29 +95,13 @@ int film_splat(nori_gpu_ctx &c, const nori_gpu_splat_desc &sd, const float *pos,
             HIP_TRY(hipMemcpyAsync(c.sh_in[0].p, pos + 2 * i0, 8 * (size_t)m, hipMemcpyHostToDevice, c.stream));
             HIP_TRY(hipMemcpyAsync(c.sh_in[1].p, val + 3 * i0, 12 * (size_t)m, hipMemcpyHostToDevice, c.stream));
             T.run([&] {
-                return launch_splat_scatter(F, m, kScatterRows, c.sh_in[0].as<float>(), c.sh_in[1].as<float>(), T.film,
-                                            T.var, T.dropped, c.stream);
+                return launch_splat_scatter(F, m, kScatterRows, c.sh_in[0].as<float>(), c.sh_in[1].as<float>(), T.out.film,
+                                            T.out.var, T.dropped, c.stream);
             });
         }
     }
-    const uint64_t dropped = T.finish();
-    splat_stats(c, t0, sd.n, dropped, T.ms, stats);
+    T.finish(t0, sd.n, stats);
     return NORI_OK;
-}
-
-// Passes folded by one work-group of k_splat_pos (NORI_SPLAT_POS_PASSES
-// overrides): about kPosTargetWgs work-groups over the launch.  A work-group
-// pays for its tile once -- zeroing it and the sweep of (32+2B)^2 x 4 atomics
-// into the film -- whatever it folds, so few long work-groups beat many short
-// ones: cbox 512x512, 8 passes, 1 / 2 / 4 / 8 passes per work-group 0.77 /
-// 0.50 / 0.30 / 0.18 ms.  256 is also the target of the path
-// integrators' splat (render.hip splat_passes).
-constexpr uint64_t kPosTargetWgs = 256;
-uint32_t passes_per_wg(uint32_t np, size_t nblocks) {
-    uint64_t v = ((uint64_t)np * nblocks + kPosTargetWgs - 1) / kPosTargetWgs;
-    if (const char *e = std::getenv("NORI_SPLAT_POS_PASSES"))
-        if (std::atoll(e) > 0) v = (uint64_t)std::atoll(e);
-    return (uint32_t)std::min<uint64_t>(std::max<uint64_t>({v, 1, ((uint64_t)np + 65534) / 65535}), np);
 }
 
 int film_splat_passes(nori_gpu_ctx &c, const nori_gpu_render_desc &rd, const float *pos, const float *val, float *rgbw,
@@ -175,15 +121,17 @@ int film_splat_passes(nori_gpu_ctx &c, const nori_gpu_render_desc &rd, const flo
     if (M == 0) throw NoriException(NORI_ERR_INVALID, std::string(name) + ": nothing to do (no blocks)");
     const FilmGeom F = film_geom(c);
     const uint64_t WH = (uint64_t)F.W * (uint64_t)F.H;
+    const char *per_wg = std::getenv("NORI_SPLAT_POS_PASSES");
     T.begin();
     if (rd.output_on_device) {
         T.run([&] {
-            return launch_splat_pos(F, c.blocks.as<int4>(), nblocks, passes, passes_per_wg(passes, nblocks), WH, pos, val,
-                                    T.film, T.var, T.dropped, c.stream);
+            return launch_splat_pos(F, c.blocks.as<int4>(), nblocks, passes, passes_per_wg(passes, nblocks, per_wg), WH, pos,
+                                    val, T.out.film, T.out.var, T.dropped, c.stream);
         });
     } else {
         // whole passes: as many as fit NORI_QUERY_CHUNK samples, at least one
-        const uint32_t kp = (uint32_t)std::min<uint64_t>(passes, std::max<uint64_t>(1, query_chunk() / WH));
+        const uint64_t most = query_chunk(std::getenv("NORI_QUERY_CHUNK"));
+        const uint32_t kp = (uint32_t)std::min<uint64_t>(passes, std::max<uint64_t>(1, most / WH));
         c.sh_in[0].ensure(8 * (size_t)kp * WH);
         c.sh_in[1].ensure(12 * (size_t)kp * WH);
         for (uint32_t k0 = 0; k0 < passes; k0 += kp) {
@@ -192,13 +140,13 @@ int film_splat_passes(nori_gpu_ctx &c, const nori_gpu_render_desc &rd, const flo
             HIP_TRY(hipMemcpyAsync(c.sh_in[0].p, pos + 2 * i0, 8 * m, hipMemcpyHostToDevice, c.stream));
             HIP_TRY(hipMemcpyAsync(c.sh_in[1].p, val + 3 * i0, 12 * m, hipMemcpyHostToDevice, c.stream));
             T.run([&] {
-                return launch_splat_pos(F, c.blocks.as<int4>(), nblocks, np, passes_per_wg(np, nblocks), WH,
-                                        c.sh_in[0].as<float>(), c.sh_in[1].as<float>(), T.film, T.var, T.dropped, c.stream);
+                return launch_splat_pos(F, c.blocks.as<int4>(), nblocks, np, passes_per_wg(np, nblocks, per_wg), WH,
+                                        c.sh_in[0].as<float>(), c.sh_in[1].as<float>(), T.out.film, T.out.var, T.dropped,
+                                        c.stream);
             });
         }
     }
-    const uint64_t dropped = T.finish();
-    splat_stats(c, t0, (uint64_t)passes * M, dropped, T.ms, stats);
+    T.finish(t0, (uint64_t)passes * M, stats);
     return NORI_OK;
 }
 

@@ -25,8 +25,7 @@ int li(nori_gpu_ctx &c, const nori_gpu_li_desc &ld, const float *rays, const uin
         if (ids) require_device_ptr(ids, "nori_gpu_li: on_device with stream_ids that are not device memory");
         require_device_ptr(out, "nori_gpu_li: on_device with an out that is not device memory");
     }
-    for (int k = 0; k < 2; ++k)
-        if (!c.q_ev[k]) HIP_TRY(hipEventCreate(&c.q_ev[k]));
+    c.clock.reset(true);
     // closest-hit rays, shadow rays, invalid rows: summed on the device over the call's launches
     c.li_count.ensure(3 * sizeof(unsigned long long));
     HIP_TRY(hipMemsetAsync(c.li_count.p, 0, 3 * sizeof(unsigned long long), c.stream));
@@ -38,7 +37,6 @@ int li(nori_gpu_ctx &c, const nori_gpu_li_desc &ld, const float *rays, const uin
     a.counters = c.li_count.as<unsigned long long>();
     c.cancel = 0;
     c.report(0.0);
-    double kms = 0.0;
     bool cancelled = false;
     // rows [i0, i0 + m) of the call from the device arrays r, s (or null) into o
     auto run = [&](uint64_t i0, uint32_t m, const float4 *r, const uint64_t *s, float *o) {
@@ -47,15 +45,11 @@ int li(nori_gpu_ctx &c, const nori_gpu_li_desc &ld, const float *rays, const uin
         a.out = o;
         a.n = m;
         a.stream_base = ld.stream_base + i0;
-        HIP_TRY(hipEventRecord(c.q_ev[0], c.stream));
-        HIP_TRY(launch_li(c.S, a, c.stack, c.stream));
-        HIP_TRY(hipEventRecord(c.q_ev[1], c.stream));
+        c.clock.span(c.stream, kKindShade, [&] { return launch_li(c.S, a, c.stack, c.stream); });
     };
     auto finish = [&](uint64_t done) {  // (the stream's work up to here)
         HIP_TRY(hipStreamSynchronize(c.stream));
-        float ms = 0.0f;
-        HIP_TRY(hipEventElapsedTime(&ms, c.q_ev[0], c.q_ev[1]));
-        kms += ms;
+        c.clock.collect();
         c.report((double)done / n);
     };
     if (ld.on_device) {
@@ -73,7 +67,7 @@ int li(nori_gpu_ctx &c, const nori_gpu_li_desc &ld, const float *rays, const uin
     } else {
         // a host `out` is left unchanged by a cancelled call: the chunks are
         // collected here and copied out at the end
-        const uint32_t chunk = std::min(std::min(n, query_chunk()), kLiLaunchRows);
+        const uint32_t chunk = std::min(std::min(n, query_chunk(std::getenv("NORI_QUERY_CHUNK"))), kLiLaunchRows);
         c.q_rays.ensure(32 * (size_t)chunk);
         if (ids) c.sh_in[0].ensure(8 * (size_t)chunk);
         c.sh_out.ensure(12 * (size_t)chunk);
@@ -99,15 +93,12 @@ int li(nori_gpu_ctx &c, const nori_gpu_li_desc &ld, const float *rays, const uin
     HIP_TRY(hipMemcpyAsync(cnt, c.li_count.p, sizeof(cnt), hipMemcpyDeviceToHost, c.stream));
     HIP_TRY(hipStreamSynchronize(c.stream));
     c.report(1.0);
-    if (stats) {
-        std::memset(stats, 0, sizeof(*stats));
-        scene_stats(c, t0, stats);
+    if (begin_stats(c, t0, stats)) {
         stats->samples = n;
         stats->rays_closest = cnt[0];
         stats->rays_shadow = cnt[1];
         stats->invalid_samples = cnt[2];
-        stats->stream_parts = 1;
-        stats->ms_shade = kms;  // k_li: the whole integrator
+        stats->ms_shade = c.clock.ms[kKindShade];  // k_li: the whole integrator
     }
     if (cancelled) return fail(NORI_ERR_CANCELLED, "nori_gpu_li was cancelled");
     return NORI_OK;

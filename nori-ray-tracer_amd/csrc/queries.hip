@@ -2,7 +2,6 @@
 // feature buffers, ray and hit-record queries, camera rays, the shading
 // queries and the samplers' uniforms; and the hit record's host statement.
 #include <algorithm>
-#include <array>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -23,7 +22,7 @@ PassChunks pass_chunks(nori_gpu_ctx &c, const nori_gpu_render_desc &rd, const ch
     work_lists(c, rd);
     const uint32_t M = (uint32_t)c.hpixels.size(), passes = rd.pass_count ? rd.pass_count : c.spp;
     if (passes == 0 || M == 0) throw NoriException(NORI_ERR_INVALID, nothing);
-    return {M, passes, (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(passes, ((uint64_t)1 << 24) / M))};
+    return {M, passes, pass_chunk(passes, M)};
 }
 
 // nori_gpu_render_features: k_features over the selected blocks' pixels, in
@@ -47,8 +46,7 @@ int render_features(nori_gpu_ctx &c, const nori_gpu_render_desc &rd, float *feat
     }
     c.cancel = 0;
     c.report(0.0);
-    Timers tm;
-    std::vector<std::array<hipEvent_t, 2>> spans;
+    KernelClock clk(rd.timing != 0);
     uint64_t done = 0;
     bool cancelled = false;
     for (uint32_t p0 = 0; p0 < passes; p0 += chunk) {
@@ -57,52 +55,26 @@ int render_features(nori_gpu_ctx &c, const nori_gpu_render_desc &rd, float *feat
             break;
         }
         const uint32_t np = std::min(chunk, passes - p0);
-        std::array<hipEvent_t, 2> ev{};
-        if (rd.timing) {
-            for (auto &e : ev) e = tm.get();
-            HIP_TRY(hipEventRecord(ev[0], c.stream));
-        }
-        HIP_TRY(launch_features(c.S, c.pixels.as<uint32_t>(), M, rd.pass_begin + p0, np, rd.seed, dev, c.stack,
-                                c.stream));
-        if (rd.timing) {
-            HIP_TRY(hipEventRecord(ev[1], c.stream));
-            spans.push_back(ev);
-        }
+        clk.span(c.stream, kKindShade, [&, M = M] {
+            return launch_features(c.S, c.pixels.as<uint32_t>(), M, rd.pass_begin + p0, np, rd.seed, dev, c.stack, c.stream);
+        });
         HIP_TRY(hipStreamSynchronize(c.stream));
         done += (uint64_t)np * M;
         c.report((double)(p0 + np) / passes);
     }
-    double kms = 0.0;
-    for (const auto &e : spans) {
-        float a = 0;
-        HIP_TRY(hipEventElapsedTime(&a, e[0], e[1]));
-        kms += a;
-    }
+    clk.collect();
     if (!rd.output_on_device && !cancelled)
         HIP_TRY(hipMemcpy(features, dev, n * sizeof(float), hipMemcpyDeviceToHost));
     c.report(1.0);
-    if (stats) {
-        std::memset(stats, 0, sizeof(*stats));
-        scene_stats(c, t0, stats);
+    if (begin_stats(c, t0, stats)) {
         stats->samples = done;
         stats->rays_closest = done;  // one primary ray per sample
-        stats->stream_parts = 1;
-        stats->ms_shade = kms;  // k_features
+        stats->ms_shade = clk.ms[kKindShade];  // k_features
     }
     if (cancelled) return fail(NORI_ERR_CANCELLED, "rendering was cancelled");
     return NORI_OK;
 }
 
-}  // namespace
-// NORI_QUERY_CHUNK: the most elements of a host array staged at once (ctx.h; film_splat.hip reads it too)
-uint32_t query_chunk() {
-    if (const char *e = std::getenv("NORI_QUERY_CHUNK")) {
-        const long long v = std::atoll(e);
-        if (v > 0) return (uint32_t)std::min<long long>(v, 0xFFFFFFFFll);
-    }
-    return 1u << 22;
-}
-namespace {
 // nori_gpu_query: launch_trace (the kernels of nori_gpu_trace), then k_surface
 // on its hits.  Device buffers are used in place; host arrays pass through the
 // context's staging buffers in chunks of at most NORI_QUERY_CHUNK rays.
@@ -111,25 +83,11 @@ int query(nori_gpu_ctx &c, const nori_gpu_query_desc &qd, const float *rays, nor
     const auto t0 = std::chrono::steady_clock::now();
     HIP_TRY(hipSetDevice(c.device));
     const uint32_t n = qd.n;
-    if (stats)
-        for (auto &e : c.q_ev)
-            if (!e) HIP_TRY(hipEventCreate(&e));
-    double ms_trace = 0.0, ms_surf = 0.0;
+    c.clock.reset(stats != nullptr);
     // one chunk on the device: rays r -> hits h (-> records s)
     auto run = [&](const float4 *r, uint32_t m, float4 *h, float4 *s) {
-        if (stats) HIP_TRY(hipEventRecord(c.q_ev[0], c.stream));
-        HIP_TRY(launch_trace(c.S, r, m, qd.any_hit, h, c.stack, c.stream, &c.rtc));
-        if (stats) HIP_TRY(hipEventRecord(c.q_ev[1], c.stream));
-        if (s) HIP_TRY(launch_surface(c.S, r, h, m, s, c.stream));
-        if (stats) HIP_TRY(hipEventRecord(c.q_ev[2], c.stream));
-    };
-    auto elapsed = [&] {  // (after the stream has been synchronised)
-        if (!stats) return;
-        float a = 0.0f, b = 0.0f;
-        HIP_TRY(hipEventElapsedTime(&a, c.q_ev[0], c.q_ev[1]));
-        HIP_TRY(hipEventElapsedTime(&b, c.q_ev[1], c.q_ev[2]));
-        ms_trace += a;
-        ms_surf += b;
+        c.clock.span(c.stream, kKindExtend, [&] { return launch_trace(c.S, r, m, qd.any_hit, h, c.stack, c.stream, &c.rtc); });
+        if (s) c.clock.span(c.stream, kKindShade, [&] { return launch_surface(c.S, r, h, m, s, c.stream); }, true);
     };
     if (qd.on_device) {
         float4 *h = reinterpret_cast<float4 *>(hits);
@@ -139,9 +97,9 @@ int query(nori_gpu_ctx &c, const nori_gpu_query_desc &qd, const float *rays, nor
         }
         run(reinterpret_cast<const float4 *>(rays), n, h, reinterpret_cast<float4 *>(surf));
         HIP_TRY(hipStreamSynchronize(c.stream));
-        elapsed();
+        c.clock.collect();
     } else {
-        const uint32_t chunk = std::min(n, query_chunk());
+        const uint32_t chunk = std::min(n, query_chunk(std::getenv("NORI_QUERY_CHUNK")));
         c.q_rays.ensure(32 * (size_t)chunk);
         c.q_hits.ensure(16 * (size_t)chunk);
         if (surf) c.q_surf.ensure(64 * (size_t)chunk);
@@ -152,16 +110,13 @@ int query(nori_gpu_ctx &c, const nori_gpu_query_desc &qd, const float *rays, nor
             if (hits) HIP_TRY(hipMemcpyAsync(hits + i0, c.q_hits.p, 16 * (size_t)m, hipMemcpyDeviceToHost, c.stream));
             if (surf) HIP_TRY(hipMemcpyAsync(surf + i0, c.q_surf.p, 64 * (size_t)m, hipMemcpyDeviceToHost, c.stream));
             HIP_TRY(hipStreamSynchronize(c.stream));
-            elapsed();
+            c.clock.collect();
         }
     }
-    if (stats) {
-        std::memset(stats, 0, sizeof(*stats));
-        scene_stats(c, t0, stats);
+    if (begin_stats(c, t0, stats)) {
         (qd.any_hit ? stats->rays_shadow : stats->rays_closest) = n;
-        stats->stream_parts = 1;
-        stats->ms_extend = ms_trace;
-        stats->ms_shade = ms_surf;  // k_surface
+        stats->ms_extend = c.clock.ms[kKindExtend];
+        stats->ms_shade = c.clock.ms[kKindShade];  // k_surface
     }
     return NORI_OK;
 }
@@ -221,7 +176,7 @@ int shading_call(nori_gpu_ctx &c, const char *name, const nori_gpu_shading_desc 
         HIP_TRY(hipStreamSynchronize(c.stream));
         return NORI_OK;
     }
-    const uint32_t chunk = std::min(n, query_chunk());
+    const uint32_t chunk = std::min(n, query_chunk(std::getenv("NORI_QUERY_CHUNK")));
     for (int k = 0; k < 3; ++k)
         if (in[k].p) c.sh_in[k].ensure(in[k].stride * (size_t)chunk);
     c.sh_out.ensure(out_stride * (size_t)chunk);

@@ -7,8 +7,12 @@
 // and the shade kernel refills finished slots from a device work counter, so
 // the GPU stays full until the last sample.  Radiance accumulates per sample
 // record; after the pool drains, k_splat applies ImageBlock::put.
+//
+// render() reads top to bottom as its steps: Wavefront's constructor plans the
+// call (render_plan.h) and takes its views of the context's buffers; per chunk
+// of passes, pool_part_views, then enqueue_iteration and wait_iteration until
+// every work id is handed out, run_tail, read_back and debug_report.
 #include <algorithm>
-#include <array>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -20,6 +24,9 @@
 
 namespace nori {
 namespace {
+
+static_assert(kPlanSeg == kSeg, "render_plan.h and seg_index.h disagree on the segment size");
+static_assert(kPlanChanShift == kChanShift, "render_plan.h and dev_scene.h disagree on the work id's bits");
 
 void ensure_pool(nori_gpu_ctx &c, uint32_t pool) {
     if (pool <= c.pool_cap) return;
@@ -47,127 +54,39 @@ PathQueue queue_of(nori_gpu_ctx &c, int b) {
     return q;
 }
 
-constexpr int kRing = 16;     // readback ring entries
-constexpr int kLookahead = 6;    // iterations queued ahead of the termination check
-constexpr int kLookaheadEnd = 2; // ... once work streams run dry
-// NORI_LOOKAHEAD=n (0 .. 8) replaces kLookahead.  The termination check reads
-// the done flag as the device has set it by now, which may be up to `lag`
-// iterations further than the event just waited for: how many iterations a
-// render launches past the one that handed out the last work id (and so how
-// its rays divide between the loop and the finisher) depends on how far the
-// host runs ahead of the device.  With 0 the host waits for every iteration
-// before it reads the flag, and the counts are the same in every run (the
-// tests that compare two renders' statistics exactly use it).
-int lookahead() {
-    const char *e = std::getenv("NORI_LOOKAHEAD");
-    const int v = e ? std::atoi(e) : kLookahead;
-    return v < 0 ? 0 : v > 8 ? 8 : v;
-}
-
-// NORI_POOL_PARTS: independent pool parts on their own streams (1..kMaxParts).
-// Default 3: each part's launches wait for their own slowest walks / longest
-// lanes, and three streams keep the chip busy in between (C3: 2 parts 619,
-// 3 parts 651, 4 parts 499 Msamples/s -- 4 streams exceed the hardware
-// queues; table scene 517 -> 555; C2 4563 -> 4658; 64-spp share 3026 ->
-// 3089; C4 and C5 within 1 %).
-// Renders whose shade kernel traces its own extension rays (ext_loop): 2.
-// An iteration is one launch there, so no part's scan is left to slip under
-// another part's shade launch (C2, 1M pool: 2 parts 6529-6637 Msamples/s;
-// 2M pool: 1 part 5579-5615, 2 parts 6404-6460, 3 parts 6311-6410).
-uint32_t pool_parts(bool ext_loop) {
-    const uint32_t def = ext_loop ? 2u : 3u;
-    const char *e = std::getenv("NORI_POOL_PARTS");
-    const long v = e ? std::atol(e) : (long)def;
-    return (uint32_t)(v >= 1 && v <= kMaxParts ? v : def);
-}
-// Sample passes folded by one splat work-group.  Default: about one
-// work-group per CU over the whole launch (passes x blocks / 256), so the
-// splat leaves most of the chip to the tail finisher it overlaps with
-// (cbox 512x512@512: 256 blocks x 512 passes per work-group, splat 3.0 ms and
-// finisher 3.6 ms vs 4.7 / 5.2 ms at 32 passes).  NORI_SPLAT_PASSES overrides.
-// The one-bounce integrators' splat has no finisher beside it: it targets
-// 4096 work-groups instead.
-uint32_t splat_passes(uint32_t np, size_t nblocks, uint32_t target_wgs = 256) {
-    const char *e = std::getenv("NORI_SPLAT_PASSES");
-    long v = e ? std::atol(e) : (long)(((uint64_t)np * nblocks + target_wgs - 1) / target_wgs);
-    if (v < 1) v = 1;
-    return (uint32_t)std::min<long>(v, np);
-}
-// Per-pixel sample statistics (render_desc.variance_out): the device buffer
-// the kernels add into -- the caller's own when it is device memory, else a
-// zeroed scratch buffer that var_finish adds into the host array.
-float *var_begin(nori_gpu_ctx &c, const nori_gpu_render_desc &rd) {
-    if (!rd.variance_out) return nullptr;
-    if (rd.output_on_device) return rd.variance_out;
-    const size_t n = 8 * (size_t)c.S.W * (size_t)c.S.H;
-    c.varbuf.ensure(n * sizeof(float));
-    HIP_TRY(hipMemsetAsync(c.varbuf.p, 0, n * sizeof(float), c.stream));
-    return c.varbuf.as<float>();
-}
-void var_finish(nori_gpu_ctx &c, const nori_gpu_render_desc &rd, bool cancelled) {
-    if (!rd.variance_out || rd.output_on_device || cancelled) return;
-    const size_t n = 8 * (size_t)c.S.W * (size_t)c.S.H;
-    std::vector<float> h(n);
-    HIP_TRY(hipMemcpy(h.data(), c.varbuf.p, n * sizeof(float), hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < n; ++i) rd.variance_out[i] += h[i];
-}
+constexpr int kRing = 16;         // readback ring entries
+constexpr int kLookaheadEnd = 2;  // iterations queued ahead of the termination check once work streams run dry
 
 // normals / av / direct*: no path pool -- per chunk of passes, k_direct runs
 // every sample start to end and writes its record, then k_splat filters them.
-int render_one_bounce(nori_gpu_ctx &c, const nori_gpu_render_desc &rd, const std::vector<uint32_t> &pixels,
-                      const std::vector<int4> &blocks, float *rgbw_out, nori_gpu_stats *stats,
+int render_one_bounce(nori_gpu_ctx &c, const nori_gpu_render_desc &rd, float *rgbw_out, nori_gpu_stats *stats,
                       std::chrono::steady_clock::time_point t0) {
     const DevScene &S = c.S;
-    const int W = S.W, H = S.H, B = S.border;
-    const uint32_t M = (uint32_t)pixels.size(), passes = rd.pass_count;
-    const size_t rec_budget = (size_t)4 << 30;
-    uint32_t chunk = (uint32_t)std::max<size_t>(1, std::min<size_t>(passes, rec_budget / (16 * (size_t)M)));
-    // work ids (record indices) < 2^29: the path queue keeps a chromatic
-    // sample's colour channel in bits 29-30 of the same word (kWorkMask)
-    chunk = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(chunk, ((uint64_t)1 << kChanShift) / M));
+    const uint32_t M = (uint32_t)c.hpixels.size(), nblocks = (uint32_t)c.hblocks.size(), passes = rd.pass_count;
+    const uint32_t chunk = record_chunk(passes, M, (size_t)4 << 30);
     c.rec.ensure(16 * (size_t)chunk * M);
     c.counters.ensure(sizeof(Counters));
-    const size_t film_elems = 4 * (size_t)(W + 2 * B) * (H + 2 * B);
-    float *film = nullptr;
-    if (rd.output_on_device) {
-        film = rgbw_out;
-    } else {
-        c.film.ensure(film_elems * sizeof(float));
-        film = c.film.as<float>();
-        HIP_TRY(hipMemsetAsync(film, 0, film_elems * sizeof(float), c.stream));
-    }
+    FilmOut out(c, rd.output_on_device != 0, rgbw_out, rd.variance_out);
+    out.begin();
     Counters *C = c.counters.as<Counters>();
     HIP_TRY(hipMemsetAsync(C, 0, sizeof(Counters), c.stream));
     if (!c.in_rounds) c.cancel = 0;
     c.report(0.0);
-    Timers tm;
-    const bool timing = rd.timing != 0;
-    double kms[2] = {0, 0};
-    std::vector<std::array<hipEvent_t, 3>> spans;
+    KernelClock clk(rd.timing != 0);
     uint64_t done = 0;
     bool cancelled = false;
-    float *var = var_begin(c, rd);
     for (uint32_t p0 = 0; p0 < passes; p0 += chunk) {
         if (c.cancel.load()) {
             cancelled = true;
             break;
         }
         const uint32_t np = std::min(chunk, passes - p0);
-        WorkDesc wd{(uint64_t)np * M, M, rd.pass_begin + p0, c.pixels.as<uint32_t>(), rd.seed, 0, nullptr, 1, 0, var};
-        SplatDesc sd{M, np, rd.pass_begin + p0, std::max<uint32_t>(1, splat_passes(np, blocks.size(), 4096)), c.blocks.as<int4>(),
-                     rd.seed, var};
-        std::array<hipEvent_t, 3> ev{};
-        if (timing) {
-            for (auto &e : ev) e = tm.get();
-            HIP_TRY(hipEventRecord(ev[0], c.stream));
-        }
-        HIP_TRY(launch_direct(S, wd, c.rec.as<float4>(), C, c.stack, c.stream));
-        if (timing) HIP_TRY(hipEventRecord(ev[1], c.stream));
-        HIP_TRY(launch_splat(S, c.rec.as<float4>(), sd, (uint32_t)blocks.size(), film, C, c.stream));
-        if (timing) {
-            HIP_TRY(hipEventRecord(ev[2], c.stream));
-            spans.push_back(ev);
-        }
+        WorkDesc wd{(uint64_t)np * M, M, rd.pass_begin + p0, c.pixels.as<uint32_t>(), rd.seed, 0, nullptr, 1, 0, out.var};
+        SplatDesc sd{M, np, rd.pass_begin + p0, splat_passes(np, nblocks, 4096, std::getenv("NORI_SPLAT_PASSES")),
+                     c.blocks.as<int4>(), rd.seed, out.var};
+        clk.span(c.stream, kKindShade, [&] { return launch_direct(S, wd, c.rec.as<float4>(), C, c.stack, c.stream); });
+        clk.span(c.stream, kKindSplat,
+                 [&] { return launch_splat(S, c.rec.as<float4>(), sd, nblocks, out.film, C, c.stream); }, true);
         HIP_TRY(hipStreamSynchronize(c.stream));
         done += wd.total;
         c.report((double)(p0 + np) / passes);
@@ -175,34 +94,324 @@ int render_one_bounce(nori_gpu_ctx &c, const nori_gpu_render_desc &rd, const std
     Counters hc;
     HIP_TRY(hipMemcpyAsync(&hc, C, sizeof(Counters), hipMemcpyDeviceToHost, c.stream));
     HIP_TRY(hipStreamSynchronize(c.stream));
-    for (const auto &e : spans) {
-        float a = 0, b = 0;
-        HIP_TRY(hipEventElapsedTime(&a, e[0], e[1]));
-        HIP_TRY(hipEventElapsedTime(&b, e[1], e[2]));
-        kms[0] += a;
-        kms[1] += b;
-    }
-    if (!rd.output_on_device && !cancelled) {
-        std::vector<float> hf(film_elems);
-        HIP_TRY(hipMemcpy(hf.data(), film, film_elems * sizeof(float), hipMemcpyDeviceToHost));
-        for (size_t i = 0; i < film_elems; ++i) rgbw_out[i] += hf[i];
-    }
-    var_finish(c, rd, cancelled);
+    clk.collect();
+    out.finish(cancelled);
     c.report(1.0);
-    if (stats) {
-        std::memset(stats, 0, sizeof(*stats));
-        scene_stats(c, t0, stats);
+    if (begin_stats(c, t0, stats)) {
         stats->samples = done;
         stats->invalid_samples = hc.invalid;
         stats->rays_closest = hc.direct_rays[0];
         stats->rays_shadow = hc.direct_rays[1];
-        stats->iterations = 0;
-        stats->stream_parts = 1;
-        stats->ms_shade = kms[0];  // k_direct: the whole integrator
-        stats->ms_splat = kms[1];
+        stats->ms_shade = clk.ms[kKindShade];  // k_direct: the whole integrator
+        stats->ms_splat = clk.ms[kKindSplat];
     }
     if (cancelled) return fail(NORI_ERR_CANCELLED, "rendering was cancelled");
     return NORI_OK;
+}
+
+// A pool part's views of the queues and its stream.  The pool is split into
+// independent parts (segments never interact), each driven on its own stream:
+// the memory-bound shade launch of one part overlaps the VALU-bound traversal
+// of another.
+struct PoolPart {
+    hipStream_t st;
+    uint32_t G;  // its segments
+    PathQueue Q[2];
+    ShadowQueue sq;
+    SegState seg;
+    WorkDesc wd;
+};
+
+// One wavefront render: the plan, the views of the context's buffers, the
+// sums over its chunks of passes, and the chunk in flight.
+struct Wavefront {
+    nori_gpu_ctx &c;
+    const nori_gpu_render_desc &rd;
+    const DevScene &S;
+    DevScene Sk;  // ... as k_shade sees it: ext_inline only where the loop relies on it
+    const uint32_t M, nblocks, passes;
+    const bool timing, ext_loop;
+    uint32_t pool, chunk, parts, G;
+    PartSplit split;
+    Counters *C;
+    PathQueue Q[2];
+    ShadowQueue sq;
+    SegState seg;
+    FilmOut out;
+    KernelClock clk;
+    uint64_t done_before = 0, rays_c = 0, rays_s = 0, invalid = 0, iters = 0, finish_rays = 0, samples_started = 0;
+    bool cancelled = false;
+    // the chunk in flight
+    uint32_t p0 = 0, np = 0;
+    WorkDesc wd{};
+    PoolPart part[kMaxParts];
+    int last_out = 0;
+    uint64_t lag = 0;
+    // NORI_DEBUG: host time spent enqueuing vs waiting on the ring events
+    // (a wait that returns at once means the device ran dry of work)
+    const bool dbg = debug_log();
+    double t_enq = 0.0, t_wait = 0.0, t_mark = 0.0;
+    uint32_t idle_waits = 0;
+
+    Wavefront(nori_gpu_ctx &ctx, const nori_gpu_render_desc &desc, float *rgbw_out);
+    hipStream_t stream_of(uint32_t h) const { return h ? c.parts[h] : c.stream; }
+};
+
+double now_us() {
+    return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+
+// The plan (pool, record chunk, parts: render_plan.h), the buffers it needs and the film target.
+Wavefront::Wavefront(nori_gpu_ctx &ctx, const nori_gpu_render_desc &desc, float *rgbw_out)
+    : c(ctx), rd(desc), S(ctx.S), Sk(ctx.S), M((uint32_t)ctx.hpixels.size()), nblocks((uint32_t)ctx.hblocks.size()),
+      passes(desc.pass_count), timing(desc.timing != 0),
+      // S.ext_inline: an iteration is the shade launch alone.  A timing render
+      // keeps the two launches (one event span per kernel), so its shade kernel
+      // reads the hits as without the flag, and it keeps the pool and the parts
+      // of the two-launch loop.
+      ext_loop(ctx.S.ext_inline != 0 && !timing), out(ctx, desc.output_on_device != 0, rgbw_out, desc.variance_out),
+      clk(timing) {
+    pool = rd.path_pool ? round_pool(rd.path_pool)
+                        : default_pool(passes, M, c.stack != 0, ext_loop, std::getenv("NORI_PATH_POOL"));
+    ensure_pool(c, pool);
+    // sample-record budget: chunks of passes, each < 2^31 records
+    chunk = record_chunk(passes, M, (size_t)6 << 30);
+    c.rec.ensure(16 * (size_t)chunk * M);
+    c.counters.ensure(sizeof(Counters));
+    out.begin();
+    if (!c.pinned) {
+        // host-mapped, coherent: the shade kernel stores the completion flag here
+        HIP_TRY(hipHostMalloc((void **)&c.pinned, 256, hipHostMallocMapped | hipHostMallocCoherent));
+        HIP_TRY(hipHostGetDevicePointer((void **)&c.pinned_dev, c.pinned, 0));
+        for (auto &r : c.ring) {
+            r.resize(kRing);
+            for (auto &e : r) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        }
+    }
+    C = c.counters.as<Counters>();
+    sq = ShadowQueue{c.sq[0].as<float4>(), c.sq[1].as<float4>(), c.sq[2].as<float4>()};
+    Q[0] = queue_of(c, 0);
+    Q[1] = queue_of(c, 1);
+    if (!ext_loop) Sk.ext_inline = 0;
+    G = pool / kSeg;
+    parts = std::max<uint32_t>(1, std::min<uint32_t>(pool_parts(std::getenv("NORI_POOL_PARTS"), ext_loop), G));
+    split = part_split(G, parts);
+    seg = SegState{{c.seg[0].as<uint32_t>(), c.seg[1].as<uint32_t>()}, c.seg[2].as<uint32_t>(), c.seg[3].as<uint32_t>(),
+                   c.segstats.as<uint4>()};
+}
+
+// The chunk's work and each part's views of the queues, segment state and work.
+void pool_part_views(Wavefront &w) {
+    w.wd = WorkDesc{(uint64_t)w.np * w.M, w.M, w.rd.pass_begin + w.p0, w.c.pixels.as<uint32_t>(), w.rd.seed, w.G,
+                    w.c.pinned_dev, 1, 0, w.out.var};
+    w.wd.rot = stream_rotation(w.wd.total, w.M, w.G);
+    auto q_view = [](const PathQueue &q, size_t e) {
+        return PathQueue{q.ray_o + e, q.ray_d + e, q.hit + e, q.thr + e, q.rng + e};
+    };
+    for (uint32_t h = 0; h < w.parts; ++h) {
+        PoolPart &p = w.part[h];
+        const uint32_t b0 = w.split.base[h];
+        const size_t e = (size_t)b0 * kSeg;
+        p.st = w.stream_of(h);
+        p.G = w.split.count[h];
+        p.Q[0] = q_view(w.Q[0], e);
+        p.Q[1] = q_view(w.Q[1], e);
+        p.sq = ShadowQueue{w.sq.ray_o + e, w.sq.ray_d + e, w.sq.payload + e};
+        p.seg = SegState{{w.seg.cnt[0] + b0, w.seg.cnt[1] + b0}, w.seg.shcnt + b0, w.seg.cursor + b0, w.seg.stats + b0};
+        p.wd = w.wd;
+        p.wd.b0 = b0;
+    }
+}
+
+// Iteration `it` on every part: k_shade from queue in = it & 1 into out, then
+// the traces its survivors and shadow rays still need; an event per part.
+void enqueue_iteration(Wavefront &w, uint64_t it) {
+    nori_gpu_ctx &c = w.c;
+    const DevScene &S = w.S;
+    const double te0 = w.dbg ? now_us() : 0.0;
+    const int in = (int)(it & 1), out = in ^ 1;
+    w.last_out = out;
+    float4 *rec = c.rec.as<float4>();
+    for (uint32_t h = 0; h < w.parts; ++h) {
+        PoolPart &p = w.part[h];
+        const SegState &sg = p.seg;
+        w.clk.span(p.st, kKindShade, [&] {
+            return launch_shade(w.Sk, p.Q[in], p.Q[out], p.sq, sg, in, p.wd, rec, w.C, p.G, p.st, &c.shade_rtc);
+        });
+        auto extend = [&] {
+            w.clk.span(p.st, kKindExtend, [&] { return launch_extend(S, p.Q[out], sg.cnt[out], p.G, c.stack, p.st, &c.rtc); });
+        };
+        hipError_t both_err = hipSuccess;
+        if (S.nee_inline) {  // the shadow rays were traced by k_shade itself
+            if (w.ext_loop) continue;  // ... and so will the next vertex's extension ray be
+            extend();
+            continue;
+        }
+        if (!w.timing && c.fuse_trace &&
+            launch_trace_both(S, p.Q[out], sg.cnt[out], p.sq, sg.shcnt, rec, p.G, c.stack, &c.rtc, p.st, both_err)) {
+            HIP_TRY(both_err);  // (the timed renders keep two launches: one event span per kernel)
+            continue;
+        }
+        extend();
+        w.clk.span(p.st, kKindShadow, [&] { return launch_shadow(S, p.sq, sg.shcnt, rec, p.G, c.stack, p.st, &c.rtc); });
+    }
+    ++w.iters;
+    for (uint32_t h = 0; h < w.parts; ++h) HIP_TRY(hipEventRecord(c.ring[h][it % kRing], w.part[h].st));
+    w.t_mark = w.dbg ? now_us() : 0.0;
+    w.t_enq += w.t_mark - te0;
+}
+
+// The host waits on the event from `lag` iterations back, then reads the flags
+// the shade kernel stores as the device has set them by now.  True: the loop ends
+// (every work id has been handed out, or the render was cancelled).
+bool wait_iteration(Wavefront &w, uint64_t it) {
+    nori_gpu_ctx &c = w.c;
+    if (it < w.lag) return false;
+    for (uint32_t h = 0; h < w.parts; ++h) HIP_TRY(hipEventSynchronize(c.ring[h][(it - w.lag) % kRing]));
+    if (w.dbg) {
+        const double t = now_us() - w.t_mark;
+        w.t_wait += t;
+        w.idle_waits += t < 5.0 ? 1u : 0u;
+    }
+    const uint32_t exhausted = __atomic_load_n(&c.pinned[1], __ATOMIC_ACQUIRE);
+    // the streams are running dry: queue fewer iterations ahead,
+    // so that few drain iterations (full-grid launches over a
+    // thinning pool) are already queued when the last one does
+    if (exhausted) w.lag = std::min<uint64_t>(w.lag, kLookaheadEnd);
+    c.report(std::min(1.0, (double)w.done_before / ((double)w.passes * w.M) + (double)w.np / w.passes * exhausted / w.G));
+    // every work id has been handed out: finish the remaining paths in one launch
+    if (__atomic_load_n(&c.pinned[0], __ATOMIC_ACQUIRE)) return true;
+    if (c.cancel.load()) w.cancelled = true;
+    return w.cancelled;
+}
+
+// The samples still in flight are marked pending; the film splat of all
+// the others runs on the side stream while the finisher completes the
+// pending ones and splats each itself.
+void run_tail(Wavefront &w) {
+    nori_gpu_ctx &c = w.c;
+    const DevScene &S = w.S;
+    const int lo = w.last_out;
+    float4 *rec = c.rec.as<float4>();
+    HIP_TRY(launch_mark(w.Q[lo], w.seg, lo, rec, w.G, c.stream));
+    HIP_TRY(launch_tail_prefix(w.seg, lo, w.G, c.tailpre.as<uint32_t>(), c.stream));
+    HIP_TRY(hipEventRecord(c.fork, c.stream));
+    HIP_TRY(hipStreamWaitEvent(c.side, c.fork, 0));
+    SplatDesc sd{w.M, w.np, w.rd.pass_begin + w.p0, splat_passes(w.np, w.nblocks, 256, std::getenv("NORI_SPLAT_PASSES")),
+                 c.blocks.as<int4>(), w.rd.seed, w.out.var};
+    auto splat = [&] {
+        w.clk.span(c.side, kKindSplat, [&] { return launch_splat(S, rec, sd, w.nblocks, w.out.film, w.C, c.side); });
+    };
+    auto finish = [&] {
+        w.clk.span(c.stream, kKindFinish, [&] {
+            return launch_finish(S, w.Q[lo], w.seg, lo, rec, w.wd, w.out.film, w.C, w.G, c.stack, c.tailpre.as<uint32_t>(),
+                                 c.stream);
+        });
+    };
+    // both wait for the same fork; the finisher's waves are enqueued first
+    // (c.finish_first) so that they are resident before the splat fills the CUs
+    if (c.finish_first) {
+        finish();
+        splat();
+    } else {
+        splat();
+        finish();
+    }
+    HIP_TRY(hipEventRecord(c.join, c.side));
+    HIP_TRY(hipStreamWaitEvent(c.stream, c.join, 0));
+}
+
+// The chunk's counters and per-segment statistics, through pinned staging: both
+// copies queue behind the finisher without a host round trip each (pageable
+// copies stage twice).  Returns when the chunk is complete on the device.
+Counters read_back(Wavefront &w) {
+    nori_gpu_ctx &c = w.c;
+    const size_t rb = sizeof(Counters) + 16 * (size_t)w.G;
+    if (c.readback_bytes < rb) {
+        if (c.readback) HIP_TRY(hipHostFree(c.readback));
+        c.readback = nullptr;
+        c.readback_bytes = 0;
+        HIP_TRY(hipHostMalloc((void **)&c.readback, rb, hipHostMallocDefault));
+        c.readback_bytes = rb;
+    }
+    HIP_TRY(hipMemcpyAsync(c.readback, w.C, sizeof(Counters), hipMemcpyDeviceToHost, c.stream));
+    HIP_TRY(hipMemcpyAsync(c.readback + sizeof(Counters), w.seg.stats, 16 * (size_t)w.G, hipMemcpyDeviceToHost, c.stream));
+    HIP_TRY(hipStreamSynchronize(c.stream));
+    Counters hc;
+    std::memcpy(&hc, c.readback, sizeof(Counters));
+    for (uint32_t b = 0; b < w.G; ++b) {
+        uint4 st;
+        std::memcpy(&st, c.readback + sizeof(Counters) + 16 * (size_t)b, 16);
+        w.rays_c += st.x;
+        w.rays_s += st.y;
+        w.samples_started += st.z;
+        w.finish_rays += st.w;
+    }
+    w.invalid += hc.invalid;
+    return hc;
+}
+
+// NORI_DEBUG: the chunk's loop, and the clocks of the profiling builds.
+void debug_report(const Wavefront &w, const Counters &hc) {
+    if (!w.dbg) return;
+    std::fprintf(stderr, "[nori] chunk %u: %lu iterations, finisher %u paths, longest %u rays\n", w.p0,
+                 (unsigned long)w.iters, hc.finish_paths, hc.finish_max_rays);
+    std::fprintf(stderr, "[nori] host loop: %.0f us enqueuing, %.0f us waiting; %u of the waits returned at once\n",
+                 w.t_enq, w.t_wait, w.idle_waits);
+    if (hc.prof[6])  // NORI_PROF_SHADE builds
+        std::fprintf(stderr, "[nori] shade clocks per wave: loads %.0f shade %.0f compact %.0f store %.0f regen %.0f drain %.0f (%llu waves)\n",
+                     (double)hc.prof[0] / hc.prof[6], (double)hc.prof[1] / hc.prof[6],
+                     (double)hc.prof[2] / hc.prof[6], (double)hc.prof[3] / hc.prof[6],
+                     (double)hc.prof[4] / hc.prof[6], (double)hc.prof[5] / hc.prof[6], hc.prof[6]);
+    else if (hc.prof[4])  // NORI_PROF_FINISH builds
+        std::fprintf(stderr, "[nori] finisher clocks per wave-iteration: shade %.0f shadow %.0f splat %.0f extend %.0f (%llu); "
+                     "longest wave %.3f ms over %llu iterations\n",
+                     (double)hc.prof[0] / hc.prof[4], (double)hc.prof[1] / hc.prof[4],
+                     (double)hc.prof[2] / hc.prof[4], (double)hc.prof[3] / hc.prof[4], hc.prof[4],
+                     (double)(hc.prof[5] >> 20) * 1e-5, hc.prof[5] & 0xFFFFFull);
+    if (hc.prof[14])  // NORI_PROF_GLASS builds
+        std::fprintf(stderr, "[nori] lone-lane glass chains: %llu chord bounces, %.0f ns each\n", hc.prof[14],
+                     10.0 * hc.prof[13] / hc.prof[14]);
+    if (hc.prof[12])
+        std::fprintf(stderr, "[nori] finisher late iterations (lone lanes): shade %.0f shadow %.0f splat %.0f extend %.0f ns (%llu)\n",
+                     10.0 * hc.prof[8] / hc.prof[12], 10.0 * hc.prof[9] / hc.prof[12],
+                     10.0 * hc.prof[10] / hc.prof[12], 10.0 * hc.prof[11] / hc.prof[12], hc.prof[12]);
+}
+
+// Passes [p0, p0 + np) of the render: reset, the loop over the parts' streams
+// until every work id is handed out, the tail on the whole pool, the read-back.
+void run_chunk(Wavefront &w) {
+    nori_gpu_ctx &c = w.c;
+    pool_part_views(w);
+    __atomic_store_n(&c.pinned[0], 0u, __ATOMIC_RELEASE);
+    __atomic_store_n(&c.pinned[1], 0u, __ATOMIC_RELEASE);
+    // segments whose stream is empty from the start count as exhausted
+    uint32_t empty = 0;
+    for (uint32_t b = 0; b < w.G; ++b) empty += stream_work(w.wd, b, 0) >= w.wd.total;
+    HIP_TRY(launch_reset(w.C, empty, w.seg, w.G, c.stream));
+    HIP_TRY(hipEventRecord(c.fork, c.stream));  // the part streams start after the resets above
+    for (uint32_t h = 1; h < w.parts; ++h) HIP_TRY(hipStreamWaitEvent(c.parts[h], c.fork, 0));
+    w.lag = (uint64_t)lookahead(std::getenv("NORI_LOOKAHEAD"));
+    w.t_enq = w.t_wait = 0.0;
+    w.idle_waits = 0;
+    for (uint64_t it = 0;; ++it) {
+        enqueue_iteration(w, it);
+        if (wait_iteration(w, it)) break;
+    }
+    // ext_loop: the last iteration's survivors and new samples have no hits
+    // yet; the finisher below reads them, so they are traced once here
+    for (uint32_t h = 0; w.ext_loop && !w.cancelled && h < w.parts; ++h) {
+        const PoolPart &p = w.part[h];
+        HIP_TRY(launch_extend(w.S, p.Q[w.last_out], p.seg.cnt[w.last_out], p.G, c.stack, p.st, &c.rtc));
+    }
+    for (uint32_t h = 1; h < w.parts; ++h) {  // join: the tail below runs on the whole pool
+        HIP_TRY(hipEventRecord(c.joins[h], c.parts[h]));
+        HIP_TRY(hipStreamWaitEvent(c.stream, c.joins[h], 0));
+    }
+    if (w.cancelled) return;
+    run_tail(w);
+    debug_report(w, read_back(w));
+    w.done_before += w.wd.total;
 }
 
 }  // namespace
@@ -247,355 +456,48 @@ void work_lists(nori_gpu_ctx &c, const nori_gpu_render_desc &rd) {
 int render(nori_gpu_ctx &c, const nori_gpu_render_desc &rd, float *rgbw_out, nori_gpu_stats *stats) {
     auto t0 = std::chrono::steady_clock::now();
     HIP_TRY(hipSetDevice(c.device));
-    const DevScene &S = c.S;
-    const int W = S.W, H = S.H, B = S.border;
     work_lists(c, rd);
-    const std::vector<uint32_t> &pixels = c.hpixels;
-    const std::vector<int4> &blocks = c.hblocks;
-    const uint32_t M = (uint32_t)pixels.size();
-    const uint32_t passes = rd.pass_count ? rd.pass_count : 0;
-    if (passes == 0 || M == 0) throw NoriException(NORI_ERR_INVALID, "nothing to render (pass_count or blocks empty)");
-    const bool one_bounce = S.integrator >= NORI_INTEGRATOR_NORMALS;
-    // default pool: about 1/16 of the render's samples in flight, between
-    // 1M and 4M paths (~0.9 GB of queues at 4M).  Large pools hide the shade
-    // kernel's memory latency (4M measured best among 256K..4M on cbox at 512
-    // spp); small renders -- the per-GPU share of a strong-scaled frame --
-    // spend less time draining a smaller pool (round 2, two parts, cbox 64
-    // spp: 4M 2190, 2M 2320, 1M 2400 Msamples/s; 512 spp: 4M and 2M within
-    // 1 %).  With three parts (round 3) the 64-spp share peaks at 1.25-1.5M
-    // (512K 2560, 1M 3030-3160, 1.25M 3320, 1.5M 3275-3296, 2M 3192, 3M 2952)
-    // and the 128-spp share at 2M (3989 against 3875 at 2.5M, 3773 at 3M).
-    // Since k_shade traces the shadow rays itself (round 6, nee_inline) the
-    // 64-spp share peaks at 1M again (4875 against 4702 at 1.5M, 4734 at
-    // 1.25M, 4555 at 768K; 3 reps), so the floor is 1M.  The BVH walks
-    // (C3) want about 1/8 in flight: 4M 846-851 against 807-812 at 2M
-    // (3M 796-798, 6M 796-798, 8M 839-846; 3 interleaved reps).
-    // Renders whose shade kernel traces its own extension rays (ext_loop)
-    // keep the 1M floor at every size: with one launch per iteration the
-    // smaller pool wins (C2 at 512 spp, two parts: 1M 6529-6637, 1.5M
-    // 6501-6511, 2M 6404-6460, 3M 6103-6210, 4M 6172-6180 Msamples/s; the
-    // 64-spp share: 768K 4926-4981, 1M 5054-5131, 1.5M 4884-4998).
-    if (one_bounce) return render_one_bounce(c, rd, pixels, blocks, rgbw_out, stats, t0);
+    const size_t M = c.hpixels.size();
+    if (rd.pass_count == 0 || M == 0) throw NoriException(NORI_ERR_INVALID, "nothing to render (pass_count or blocks empty)");
+    if (c.S.integrator >= NORI_INTEGRATOR_NORMALS) return render_one_bounce(c, rd, rgbw_out, stats, t0);
     if (M > kWorkMask) throw NoriException(NORI_ERR_INVALID, "frame too large: more than 2^29 pixels per pass");
-    const bool timing = rd.timing != 0;
-    // S.ext_inline: an iteration is the shade launch alone.  A timing render
-    // keeps the two launches (one event span per kernel), so its shade kernel
-    // reads the hits as without the flag, and it keeps the pool and the parts
-    // of the two-launch loop.
-    const bool ext_loop = S.ext_inline != 0 && !timing;
-    uint32_t pool = rd.path_pool;
-    if (!pool) {  // NORI_PATH_POOL: default pool size override (tuning)
-        const char *e = std::getenv("NORI_PATH_POOL");
-        if (e && std::atol(e) > 0) {
-            pool = (uint32_t)std::min<long>(std::atol(e), 1L << 26);
-        } else {
-            const uint64_t want = (uint64_t)passes * M / (c.stack ? 8 : 16);
-            pool = 1u << 20;
-            while (!ext_loop && pool < (1u << 22) && pool < want) pool <<= 1;
-        }
-    }
-    pool = std::max<uint32_t>(kSeg, (pool + kSeg - 1) / kSeg * kSeg);
-    ensure_pool(c, pool);
-    // sample-record budget: chunks of passes, each < 2^31 records
-    const size_t rec_budget = (size_t)6 << 30;
-    uint32_t chunk = (uint32_t)std::max<size_t>(1, std::min<size_t>(passes, rec_budget / (16 * (size_t)M)));
-    // work ids (record indices) < 2^29: the path queue keeps a chromatic
-    // sample's colour channel in bits 29-30 of the same word (kWorkMask)
-    chunk = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(chunk, ((uint64_t)1 << kChanShift) / M));
-    c.rec.ensure(16 * (size_t)chunk * M);
-    c.counters.ensure(sizeof(Counters));
-    const size_t film_elems = 4 * (size_t)(W + 2 * B) * (H + 2 * B);
-    float *film = nullptr;
-    if (rd.output_on_device) {
-        film = rgbw_out;
-    } else {
-        c.film.ensure(film_elems * sizeof(float));
-        film = c.film.as<float>();
-        HIP_TRY(hipMemsetAsync(film, 0, film_elems * sizeof(float), c.stream));
-    }
-    if (!c.pinned) {
-        // host-mapped, coherent: the shade kernel stores the completion flag here
-        HIP_TRY(hipHostMalloc((void **)&c.pinned, 256, hipHostMallocMapped | hipHostMallocCoherent));
-        HIP_TRY(hipHostGetDevicePointer((void **)&c.pinned_dev, c.pinned, 0));
-        for (auto &r : c.ring) {
-            r.resize(kRing);
-            for (auto &e : r) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        }
-    }
-    Counters *C = c.counters.as<Counters>();
-    ShadowQueue sq{c.sq[0].as<float4>(), c.sq[1].as<float4>(), c.sq[2].as<float4>()};
-    PathQueue Q[2] = {queue_of(c, 0), queue_of(c, 1)};
+    Wavefront w(c, rd, rgbw_out);
     if (!c.in_rounds) c.cancel = 0;
     c.report(0.0);
-    const uint64_t total_all = (uint64_t)passes * M;
-    uint64_t done_before = 0, rays_c = 0, rays_s = 0, invalid = 0, iters = 0;
-    Timers tm;
-    struct Span {
-        hipEvent_t a, b;
-        int kind;
-    };
-    std::vector<Span> spans;
-    DevScene Sk = S;
-    if (!ext_loop) Sk.ext_inline = 0;
-    auto timed_on = [&](hipStream_t st, int kind, auto &&launch) {
-        if (!timing) {
-            HIP_TRY(launch());
-            return;
-        }
-        Span s{tm.get(), tm.get(), kind};
-        HIP_TRY(hipEventRecord(s.a, st));
-        HIP_TRY(launch());
-        HIP_TRY(hipEventRecord(s.b, st));
-        spans.push_back(s);
-    };
-    auto timed = [&](int kind, auto &&launch) { timed_on(c.stream, kind, launch); };
-    bool cancelled = false;
-    const uint32_t parts = std::max<uint32_t>(1, std::min<uint32_t>(pool_parts(ext_loop), pool / kSeg));
-    const uint32_t G = pool / kSeg;
-    SegState seg{{c.seg[0].as<uint32_t>(), c.seg[1].as<uint32_t>()}, c.seg[2].as<uint32_t>(), c.seg[3].as<uint32_t>(),
-                 c.segstats.as<uint4>()};
-    std::vector<uint4> hstats(G);
-    uint64_t finish_rays = 0, samples_started = 0;
-    float *var = var_begin(c, rd);
-    for (uint32_t p0 = 0; p0 < passes && !cancelled; p0 += chunk) {
-        uint32_t np = std::min(chunk, passes - p0);
-        WorkDesc wd{(uint64_t)np * M, M, rd.pass_begin + p0, c.pixels.as<uint32_t>(), rd.seed, G, c.pinned_dev, 1, 0,
-                    var};
-        wd.rot = stream_rotation(wd.total, M, G);
-        __atomic_store_n(&c.pinned[0], 0u, __ATOMIC_RELEASE);
-        __atomic_store_n(&c.pinned[1], 0u, __ATOMIC_RELEASE);
-        // segments whose stream is empty from the start count as exhausted
-        uint32_t empty = 0;
-        for (uint32_t b = 0; b < G; ++b) empty += stream_work(wd, b, 0) >= wd.total;
-        HIP_TRY(launch_reset(C, empty, seg, G, c.stream));
-        int last_out = 0;
-        // The pool is split into `parts` independent parts (segments never
-        // interact), each driven on its own stream: the memory-bound shade
-        // launch of one part overlaps the VALU-bound traversal of another.
-        std::vector<uint32_t> Gp(parts), base(parts);
-        for (uint32_t h = 0; h < parts; ++h) {
-            base[h] = (uint32_t)((uint64_t)G * h / parts);
-            Gp[h] = (uint32_t)((uint64_t)G * (h + 1) / parts) - base[h];
-        }
-        auto q_view = [&](const PathQueue &q, uint32_t b0) {
-            const size_t e = (size_t)b0 * kSeg;
-            return PathQueue{q.ray_o + e, q.ray_d + e, q.hit + e, q.thr + e, q.rng + e};
-        };
-        std::vector<std::array<PathQueue, 2>> Qh(parts);
-        std::vector<ShadowQueue> sqh(parts);
-        std::vector<SegState> segh(parts);
-        std::vector<WorkDesc> wdh(parts);
-        for (uint32_t h = 0; h < parts; ++h) {
-            Qh[h][0] = q_view(Q[0], base[h]);
-            Qh[h][1] = q_view(Q[1], base[h]);
-            const size_t e = (size_t)base[h] * kSeg;
-            sqh[h] = ShadowQueue{sq.ray_o + e, sq.ray_d + e, sq.payload + e};
-            segh[h] = SegState{{seg.cnt[0] + base[h], seg.cnt[1] + base[h]}, seg.shcnt + base[h],
-                               seg.cursor + base[h], seg.stats + base[h]};
-            wdh[h] = wd;
-            wdh[h].b0 = base[h];
-        }
-        HIP_TRY(hipEventRecord(c.fork, c.stream));  // the part streams start after the resets above
-        for (uint32_t h = 1; h < parts; ++h) HIP_TRY(hipStreamWaitEvent(c.parts[h], c.fork, 0));
-        uint64_t lag = (uint64_t)lookahead();
-        // NORI_DEBUG: host time spent enqueuing vs waiting on the ring events
-        // (a wait that returns at once means the device ran dry of work)
-        const bool dbg = debug_log();
-        double t_enq = 0.0, t_wait = 0.0;
-        uint32_t idle_waits = 0;
-        auto now_us = [] {
-            return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count();
-        };
-        for (uint64_t it = 0;; ++it) {
-            const double te0 = dbg ? now_us() : 0.0;
-            int in = (int)(it & 1), out = in ^ 1;
-            last_out = out;
-            for (uint32_t h = 0; h < parts; ++h) {
-                hipStream_t st = h ? c.parts[h] : c.stream;
-                const SegState &sg = segh[h];
-                timed_on(st, 2, [&] {
-                    return launch_shade(Sk, Qh[h][in], Qh[h][out], sqh[h], sg, in, wdh[h], c.rec.as<float4>(), C,
-                                        Gp[h], st, &c.shade_rtc);
-                });
-                hipError_t both_err = hipSuccess;
-                if (S.nee_inline) {  // the shadow rays were traced by k_shade itself
-                    if (ext_loop) continue;  // ... and so will the next vertex's extension ray be
-                    timed_on(st, 0, [&] { return launch_extend(S, Qh[h][out], sg.cnt[out], Gp[h], c.stack, st, &c.rtc); });
-                    continue;
-                }
-                if (!timing && c.fuse_trace &&
-                    launch_trace_both(S, Qh[h][out], sg.cnt[out], sqh[h], sg.shcnt, c.rec.as<float4>(), Gp[h], c.stack,
-                                      &c.rtc, st, both_err)) {
-                    HIP_TRY(both_err);  // (the timed renders keep two launches: one event span per kernel)
-                    continue;
-                }
-                timed_on(st, 0, [&] { return launch_extend(S, Qh[h][out], sg.cnt[out], Gp[h], c.stack, st, &c.rtc); });
-                timed_on(st, 1, [&] {
-                    return launch_shadow(S, sqh[h], sg.shcnt, c.rec.as<float4>(), Gp[h], c.stack, st, &c.rtc);
-                });
-            }
-            ++iters;
-            // an event per iteration; the host waits on the one from `lag`
-            // iterations back
-            const uint64_t ev = it;
-            for (uint32_t h = 0; h < parts; ++h)
-                HIP_TRY(hipEventRecord(c.ring[h][ev % kRing], h ? c.parts[h] : c.stream));
-            const double te1 = dbg ? now_us() : 0.0;
-            t_enq += te1 - te0;
-            if (ev >= lag) {
-                for (uint32_t h = 0; h < parts; ++h) HIP_TRY(hipEventSynchronize(c.ring[h][(ev - lag) % kRing]));
-                if (dbg) {
-                    const double w = now_us() - te1;
-                    t_wait += w;
-                    idle_waits += w < 5.0 ? 1u : 0u;
-                }
-                uint32_t exhausted = __atomic_load_n(&c.pinned[1], __ATOMIC_ACQUIRE);
-                // the streams are running dry: queue fewer iterations ahead,
-                // so that few drain iterations (full-grid launches over a
-                // thinning pool) are already queued when the last one does
-                if (exhausted) lag = std::min<uint64_t>(lag, kLookaheadEnd);
-                c.report(std::min(1.0, (double)done_before / (double)total_all +
-                                           (double)np / passes * exhausted / G));
-                // every work id has been handed out: finish the remaining paths in one launch
-                if (__atomic_load_n(&c.pinned[0], __ATOMIC_ACQUIRE)) break;
-                if (c.cancel.load()) {
-                    cancelled = true;
-                    break;
-                }
-            }
-        }
-        // ext_loop: the last iteration's survivors and new samples have no hits
-        // yet; the finisher below reads them, so they are traced once here
-        for (uint32_t h = 0; ext_loop && !cancelled && h < parts; ++h)
-            HIP_TRY(launch_extend(S, Qh[h][last_out], segh[h].cnt[last_out], Gp[h], c.stack, h ? c.parts[h] : c.stream,
-                                  &c.rtc));
-        for (uint32_t h = 1; h < parts; ++h) {  // join: the tail below runs on the whole pool
-            HIP_TRY(hipEventRecord(c.joins[h], c.parts[h]));
-            HIP_TRY(hipStreamWaitEvent(c.stream, c.joins[h], 0));
-        }
-        if (cancelled) break;
-        // The samples still in flight are marked pending; the film splat of all
-        // the others runs on the side stream while the finisher completes the
-        // pending ones and splats each itself.
-        hipStream_t splat_st = c.side;
-        HIP_TRY(launch_mark(Q[last_out], seg, last_out, c.rec.as<float4>(), G, c.stream));
-        HIP_TRY(launch_tail_prefix(seg, last_out, G, c.tailpre.as<uint32_t>(), c.stream));
-        HIP_TRY(hipEventRecord(c.fork, c.stream));
-        HIP_TRY(hipStreamWaitEvent(c.side, c.fork, 0));
-        SplatDesc sd{M, np, rd.pass_begin + p0, std::max<uint32_t>(1, splat_passes(np, blocks.size())),
-                     c.blocks.as<int4>(), rd.seed, var};
-        auto splat = [&] {
-            timed_on(splat_st, 3, [&] { return launch_splat(S, c.rec.as<float4>(), sd, (uint32_t)blocks.size(), film, C, splat_st); });
-        };
-        auto finish = [&] {
-            timed(4, [&] {
-                return launch_finish(S, Q[last_out], seg, last_out, c.rec.as<float4>(), wd, film, C, G, c.stack,
-                                     c.tailpre.as<uint32_t>(), c.stream);
-            });
-        };
-        // both wait for the same fork; the finisher's waves are enqueued first
-        // (c.finish_first) so that they are resident before the splat fills the CUs
-        if (c.finish_first) {
-            finish();
-            splat();
-        } else {
-            splat();
-            finish();
-        }
-        HIP_TRY(hipEventRecord(c.join, c.side));
-        HIP_TRY(hipStreamWaitEvent(c.stream, c.join, 0));
-        // read-back through pinned staging: both copies queue behind the
-        // finisher without a host round trip each (pageable copies stage twice)
-        const size_t rb = sizeof(Counters) + 16 * (size_t)G;
-        if (c.readback_bytes < rb) {
-            if (c.readback) HIP_TRY(hipHostFree(c.readback));
-            c.readback = nullptr;
-            c.readback_bytes = 0;
-            HIP_TRY(hipHostMalloc((void **)&c.readback, rb, hipHostMallocDefault));
-            c.readback_bytes = rb;
-        }
-        HIP_TRY(hipMemcpyAsync(c.readback, C, sizeof(Counters), hipMemcpyDeviceToHost, c.stream));
-        HIP_TRY(hipMemcpyAsync(c.readback + sizeof(Counters), seg.stats, 16 * (size_t)G, hipMemcpyDeviceToHost, c.stream));
+    for (w.p0 = 0; w.p0 < w.passes && !w.cancelled; w.p0 += w.chunk) {
+        w.np = std::min(w.chunk, w.passes - w.p0);
+        run_chunk(w);
+    }
+    if (w.samples_started != w.done_before && !w.cancelled)
+        throw NoriException(NORI_ERR_INVALID, "internal: started " + std::to_string(w.samples_started) + " of " +
+                                                  std::to_string(w.done_before) + " samples");
+    if (w.timing) {
         HIP_TRY(hipStreamSynchronize(c.stream));
-        Counters hc;
-        std::memcpy(&hc, c.readback, sizeof(Counters));
-        std::memcpy(hstats.data(), c.readback + sizeof(Counters), 16 * (size_t)G);
-        for (const uint4 &st : hstats) {
-            rays_c += st.x;
-            rays_s += st.y;
-            samples_started += st.z;
-            finish_rays += st.w;
-        }
-        invalid += hc.invalid;
-        if (debug_log())
-        {
-            std::fprintf(stderr, "[nori] chunk %u: %lu iterations, finisher %u paths, longest %u rays\n", p0,
-                         (unsigned long)iters, hc.finish_paths, hc.finish_max_rays);
-            std::fprintf(stderr, "[nori] host loop: %.0f us enqueuing, %.0f us waiting; %u of the waits returned at once\n",
-                         t_enq, t_wait, idle_waits);
-            if (hc.prof[6])  // NORI_PROF_SHADE builds
-                std::fprintf(stderr, "[nori] shade clocks per wave: loads %.0f shade %.0f compact %.0f store %.0f regen %.0f drain %.0f (%llu waves)\n",
-                             (double)hc.prof[0] / hc.prof[6], (double)hc.prof[1] / hc.prof[6],
-                             (double)hc.prof[2] / hc.prof[6], (double)hc.prof[3] / hc.prof[6],
-                             (double)hc.prof[4] / hc.prof[6], (double)hc.prof[5] / hc.prof[6], hc.prof[6]);
-            else if (hc.prof[4])  // NORI_PROF_FINISH builds
-                std::fprintf(stderr, "[nori] finisher clocks per wave-iteration: shade %.0f shadow %.0f splat %.0f extend %.0f (%llu); "
-                             "longest wave %.3f ms over %llu iterations\n",
-                             (double)hc.prof[0] / hc.prof[4], (double)hc.prof[1] / hc.prof[4],
-                             (double)hc.prof[2] / hc.prof[4], (double)hc.prof[3] / hc.prof[4], hc.prof[4],
-                             (double)(hc.prof[5] >> 20) * 1e-5, hc.prof[5] & 0xFFFFFull);
-            if (hc.prof[14])  // NORI_PROF_GLASS builds
-                std::fprintf(stderr, "[nori] lone-lane glass chains: %llu chord bounces, %.0f ns each\n", hc.prof[14],
-                             10.0 * hc.prof[13] / hc.prof[14]);
-            if (hc.prof[12])
-                std::fprintf(stderr, "[nori] finisher late iterations (lone lanes): shade %.0f shadow %.0f splat %.0f extend %.0f ns (%llu)\n",
-                             10.0 * hc.prof[8] / hc.prof[12], 10.0 * hc.prof[9] / hc.prof[12],
-                             10.0 * hc.prof[10] / hc.prof[12], 10.0 * hc.prof[11] / hc.prof[12], hc.prof[12]);
-        }
-        done_before += wd.total;
+        w.clk.collect();
     }
-    if (samples_started != done_before && !cancelled)
-        throw NoriException(NORI_ERR_INVALID, "internal: started " + std::to_string(samples_started) + " of " +
-                                                  std::to_string(done_before) + " samples");
-    double kms[5] = {0, 0, 0, 0, 0};
-    if (timing) {
-        HIP_TRY(hipStreamSynchronize(c.stream));
-        for (const Span &s : spans) {
-            float ms = 0.0f;
-            HIP_TRY(hipEventElapsedTime(&ms, s.a, s.b));
-            kms[s.kind] += ms;
-        }
-    }
-    if (!rd.output_on_device && !cancelled) {
-        std::vector<float> hf(film_elems);
-        HIP_TRY(hipMemcpy(hf.data(), film, film_elems * sizeof(float), hipMemcpyDeviceToHost));
-        for (size_t i = 0; i < film_elems; ++i) rgbw_out[i] += hf[i];
-    }
-    var_finish(c, rd, cancelled);
+    w.out.finish(w.cancelled);
     HIP_TRY(hipStreamSynchronize(c.stream));
     HIP_TRY(hipStreamSynchronize(c.side));
     for (int h = 1; h < kMaxParts; ++h) HIP_TRY(hipStreamSynchronize(c.parts[h]));
     c.report(1.0);
-    if (stats) {
-        std::memset(stats, 0, sizeof(*stats));
-        scene_stats(c, t0, stats);
-        stats->samples = done_before;
-        stats->invalid_samples = invalid;
-        stats->rays_closest = rays_c;
-        stats->rays_shadow = rays_s;
-        stats->iterations = iters;
-        stats->stream_parts = parts;
-        stats->path_pool = pool;
-        stats->ms_extend = kms[0];
-        stats->ms_shadow = kms[1];
-        stats->ms_shade = kms[2];
-        stats->ms_splat = kms[3];
-        stats->ms_finish = kms[4];
-        stats->rays_finish = finish_rays;
-        stats->nee_inline = S.nee_inline ? 1u : 0u;
-        stats->ext_inline = S.ext_inline ? 1u : 0u;
+    if (begin_stats(c, t0, stats)) {
+        stats->samples = w.done_before;
+        stats->invalid_samples = w.invalid;
+        stats->rays_closest = w.rays_c;
+        stats->rays_shadow = w.rays_s;
+        stats->iterations = w.iters;
+        stats->stream_parts = w.parts;
+        stats->path_pool = w.pool;
+        stats->ms_extend = w.clk.ms[kKindExtend];
+        stats->ms_shadow = w.clk.ms[kKindShadow];
+        stats->ms_shade = w.clk.ms[kKindShade];
+        stats->ms_splat = w.clk.ms[kKindSplat];
+        stats->ms_finish = w.clk.ms[kKindFinish];
+        stats->rays_finish = w.finish_rays;
+        stats->nee_inline = c.S.nee_inline ? 1u : 0u;
+        stats->ext_inline = c.S.ext_inline ? 1u : 0u;
     }
-    if (cancelled) return fail(NORI_ERR_CANCELLED, "rendering was cancelled");
+    if (w.cancelled) return fail(NORI_ERR_CANCELLED, "rendering was cancelled");
     return NORI_OK;
 }
 

@@ -441,6 +441,11 @@ def read_image(path):
     return out
 
 
+def _addr(a):
+    """The device address of a torch tensor or an int device address (None stays None)."""
+    return None if a is None else int(a.data_ptr() if hasattr(a, "data_ptr") else a)
+
+
 class GpuRenderer:
     """HIP context holding one scene on one device (nori_gpu_create)."""
 
@@ -479,6 +484,32 @@ class GpuRenderer:
         check(lib().nori_gpu_shade_rtc_info(self._h, C.byref(a), C.byref(c), C.byref(ms), C.byref(n)))
         return {"active": bool(a.value), "cached": bool(c.value), "ms": ms.value, "code_bytes": n.value}
 
+    def _call(self, fn, *args):
+        """fn(context, *args, stats), checked; the call's statistics become last_stats."""
+        st = _abi.Stats()
+        check(fn(self._h, *args, C.byref(st)))
+        self.last_stats = st.as_dict()
+
+    def _film_arg(self, out, device_ptr):
+        """(the film argument, the film to return) of a call that adds into a film: the device film
+        at `device_ptr`, else the host film `out` (a new one when None)."""
+        if device_ptr is not None:
+            return C.c_void_p(int(device_ptr)), None
+        if out is None:
+            out = np.zeros(self.scene.film_shape(), np.float32)
+        assert out.dtype == np.float32 and out.flags.c_contiguous and out.shape == self.scene.film_shape()
+        return out.ctypes.data_as(C.c_void_p), out
+
+    def _variance_arg(self, variance, on_device):
+        """The address of a per-pixel statistics argument: an int device address, else an (H, W, 8) array."""
+        if variance is None:
+            return None
+        if on_device:
+            return int(variance)
+        assert (isinstance(variance, np.ndarray) and variance.dtype == np.float32 and variance.flags.c_contiguous
+                and variance.shape == (self.scene.height, self.scene.width, 8))
+        return variance.ctypes.data
+
     def render(self, passes=None, pass_begin=0, blocks=None, seed=0, out=None, path_pool=0,
                device_ptr=None, timing=False, variance=None):
         """Render passes [pass_begin, pass_begin+passes) of `blocks` (all if None).
@@ -491,24 +522,10 @@ class GpuRenderer:
         into (see film_variance).
         """
         rd, ids = self._desc(passes, pass_begin, blocks, seed, path_pool, timing)
-        if variance is not None:
-            if device_ptr is not None:
-                rd.variance_out = int(variance)
-            else:
-                assert (isinstance(variance, np.ndarray) and variance.dtype == np.float32 and variance.flags.c_contiguous
-                        and variance.shape == (self.scene.height, self.scene.width, 8))
-                rd.variance_out = variance.ctypes.data
-        st = _abi.Stats()
-        if device_ptr is not None:
-            rd.output_on_device = 1
-            check(lib().nori_gpu_render(self._h, C.byref(rd), C.c_void_p(int(device_ptr)), C.byref(st)))
-            self.last_stats = st.as_dict()
-            return None
-        if out is None:
-            out = np.zeros(self.scene.film_shape(), np.float32)
-        assert out.dtype == np.float32 and out.flags.c_contiguous and out.shape == self.scene.film_shape()
-        check(lib().nori_gpu_render(self._h, C.byref(rd), out.ctypes.data_as(C.c_void_p), C.byref(st)))
-        self.last_stats = st.as_dict()
+        rd.variance_out = self._variance_arg(variance, device_ptr is not None)
+        rd.output_on_device = int(device_ptr is not None)
+        film, out = self._film_arg(out, device_ptr)
+        self._call(lib().nori_gpu_render, C.byref(rd), film)
         return out
 
     def _desc(self, passes, pass_begin, blocks, seed, path_pool, timing):
@@ -556,25 +573,11 @@ class GpuRenderer:
         errors = np.zeros(self.scene.num_blocks(), np.float32)
         ad.passes_out = passes.ctypes.data_as(C.POINTER(C.c_uint32))
         ad.error_out = _fptr(errors)
-        if variance is not None:
-            if device_ptr is not None:
-                rd.variance_out = int(variance)
-            else:
-                assert (isinstance(variance, np.ndarray) and variance.dtype == np.float32 and variance.flags.c_contiguous
-                        and variance.shape == (self.scene.height, self.scene.width, 8))
-                rd.variance_out = variance.ctypes.data
-        st = _abi.Stats()
-        if device_ptr is not None:
-            rd.output_on_device = 1
-            film = C.c_void_p(int(device_ptr))
-        else:
-            if out is None:
-                out = np.zeros(self.scene.film_shape(), np.float32)
-            assert out.dtype == np.float32 and out.flags.c_contiguous and out.shape == self.scene.film_shape()
-            film = out.ctypes.data_as(C.c_void_p)
-        check(lib().nori_gpu_render_adaptive(self._h, C.byref(rd), C.byref(ad), film, C.byref(st)))
-        self.last_stats = st.as_dict()
-        return (None if device_ptr is not None else out), passes, errors
+        rd.variance_out = self._variance_arg(variance, device_ptr is not None)
+        rd.output_on_device = int(device_ptr is not None)
+        film, out = self._film_arg(out, device_ptr)
+        self._call(lib().nori_gpu_render_adaptive, C.byref(rd), C.byref(ad), film)
+        return out, passes, errors
 
     def render_sharded(self, comm, device_ptr, passes=None, pass_begin=0, blocks=None, mode="passes", root=0,
                        seed=0, path_pool=0, timing=False, variance=None):
@@ -587,10 +590,8 @@ class GpuRenderer:
         rd, ids = self._desc(passes, pass_begin, blocks, seed, path_pool, timing)
         if variance is not None:
             rd.variance_out = int(variance)
-        st = _abi.Stats()
-        check(lib().nori_gpu_render_sharded(self._h, comm.handle, C.byref(rd), _abi.SHARD_MODES[mode], int(root),
-                                            C.c_void_p(int(device_ptr)), C.byref(st)))
-        self.last_stats = st.as_dict()
+        self._call(lib().nori_gpu_render_sharded, comm.handle, C.byref(rd), _abi.SHARD_MODES[mode], int(root),
+                   C.c_void_p(int(device_ptr)))
 
     def features(self, passes=None, pass_begin=0, blocks=None, seed=0, out=None, timing=False):
         """First-hit features of the camera samples of passes [pass_begin, pass_begin+passes) of
@@ -602,17 +603,14 @@ class GpuRenderer:
         added on the GPU and None is returned.  film_features() turns the sums into means."""
         rd, ids = self._desc(passes, pass_begin, blocks, seed, 0, timing)
         shape = (self.scene.height, self.scene.width, 8)
-        st = _abi.Stats()
         if out is not None and not isinstance(out, np.ndarray):
             rd.output_on_device = 1
-            check(lib().nori_gpu_render_features(self._h, C.byref(rd), C.c_void_p(int(out)), C.byref(st)))
-            self.last_stats = st.as_dict()
+            self._call(lib().nori_gpu_render_features, C.byref(rd), C.c_void_p(int(out)))
             return None
         if out is None:
             out = np.zeros(shape, np.float32)
         assert out.dtype == np.float32 and out.flags.c_contiguous and out.shape == shape
-        check(lib().nori_gpu_render_features(self._h, C.byref(rd), out.ctypes.data_as(C.c_void_p), C.byref(st)))
-        self.last_stats = st.as_dict()
+        self._call(lib().nori_gpu_render_features, C.byref(rd), out.ctypes.data_as(C.c_void_p))
         return out
 
     def trace(self, rays, any_hit=False):
@@ -636,15 +634,13 @@ class GpuRenderer:
         both; all 16-byte aligned, e.g. torch tensors' data_ptr()); nothing is copied and None is
         returned.  The buffers must be ready before the call (torch.cuda.synchronize())."""
         qd = _abi.QueryDesc(0, int(bool(any_hit)), 0, 0)
-        st = _abi.Stats()
         if not isinstance(rays, np.ndarray):
             if n is None:
                 raise ValueError("query: a device address needs n=")
             qd.n, qd.on_device = int(n), 1
-            check(lib().nori_gpu_query(self._h, C.byref(qd), C.c_void_p(int(rays)),
-                                       None if hits_out is None else C.c_void_p(int(hits_out)),
-                                       None if surf_out is None else C.c_void_p(int(surf_out)), C.byref(st)))
-            self.last_stats = st.as_dict()
+            self._call(lib().nori_gpu_query, C.byref(qd), C.c_void_p(int(rays)),
+                       None if hits_out is None else C.c_void_p(int(hits_out)),
+                       None if surf_out is None else C.c_void_p(int(surf_out)))
             return None
         rays = np.ascontiguousarray(rays, dtype=np.float32)
         if rays.ndim != 2 or rays.shape[1] != 8:
@@ -652,9 +648,8 @@ class GpuRenderer:
         qd.n = rays.shape[0]
         hits = np.zeros(qd.n, HIT_DTYPE)
         surf = np.zeros(qd.n, SURFACE_DTYPE) if surface and not any_hit else None
-        check(lib().nori_gpu_query(self._h, C.byref(qd), C.c_void_p(rays.ctypes.data), C.c_void_p(hits.ctypes.data),
-                                   None if surf is None else C.c_void_p(surf.ctypes.data), C.byref(st)))
-        self.last_stats = st.as_dict()
+        self._call(lib().nori_gpu_query, C.byref(qd), C.c_void_p(rays.ctypes.data), C.c_void_p(hits.ctypes.data),
+                   None if surf is None else C.c_void_p(surf.ctypes.data))
         return {"hits": hits} if surf is None else {"hits": hits, "surf": surf}
 
     def camera_rays(self, passes=None, pass_begin=0, blocks=None, seed=0, out=None):
@@ -689,9 +684,7 @@ class GpuRenderer:
             if n is None or out is None or isinstance(out, np.ndarray):
                 raise ValueError(f"{name}: device addresses need n= and a device address out=")
             sd.n, sd.on_device = int(n), 1
-            ptrs = [None if a is None else C.c_void_p(int(a.data_ptr() if hasattr(a, "data_ptr") else a))
-                    for a, _, _, _ in arrays]
-            check(fn(self._h, C.byref(sd), *ptrs, C.c_void_p(int(out.data_ptr() if hasattr(out, "data_ptr") else out))))
+            check(fn(self._h, C.byref(sd), *[C.c_void_p(_addr(a)) for a, _, _, _ in arrays], C.c_void_p(_addr(out))))
             return None
         conv = []
         for a, dt, k, opt in arrays:
@@ -768,7 +761,7 @@ class GpuRenderer:
         if out is not None and not isinstance(out, np.ndarray):
             rd.output_on_device = 1
             check(lib().nori_gpu_sample_uniforms(self._h, C.byref(rd), int(first), int(count),
-                                                 C.c_void_p(int(out.data_ptr() if hasattr(out, "data_ptr") else out))))
+                                                 C.c_void_p(_addr(out))))
             return None
         if out is None:
             out = np.zeros(shape, np.float32)
@@ -788,18 +781,13 @@ class GpuRenderer:
         stream_ids 8-byte aligned): used in place, None is returned, and the buffers must be ready
         before the call.  last_stats: samples, invalid_samples, rays_closest, rays_shadow, ms_shade."""
         ld = _abi.LiDesc(0, 0, int(seed), int(stream_base), int(first_draw), 0)
-        st = _abi.Stats()
-
-        def addr(a):
-            return None if a is None else C.c_void_p(int(a.data_ptr() if hasattr(a, "data_ptr") else a))
         if not isinstance(rays, np.ndarray):
             if isinstance(stream_ids, np.ndarray) or isinstance(out, np.ndarray):
                 raise ValueError("li: the arrays must all be numpy arrays or all be device addresses")
             if n is None or out is None:
                 raise ValueError("li: device addresses need n= and a device address out=")
             ld.n, ld.on_device = int(n), 1
-            check(lib().nori_gpu_li(self._h, C.byref(ld), addr(rays), addr(stream_ids), addr(out), C.byref(st)))
-            self.last_stats = st.as_dict()
+            self._call(lib().nori_gpu_li, C.byref(ld), *[C.c_void_p(_addr(a)) for a in (rays, stream_ids, out)])
             return None
         rays = np.ascontiguousarray(rays, dtype=np.float32)
         if rays.ndim != 2 or rays.shape[1] != 8:
@@ -815,17 +803,13 @@ class GpuRenderer:
         if out is None:
             out = np.zeros((ld.n, 3), np.float32)
         assert isinstance(out, np.ndarray) and out.dtype == np.float32 and out.flags.c_contiguous and out.shape == (ld.n, 3)
-        check(lib().nori_gpu_li(self._h, C.byref(ld), C.c_void_p(rays.ctypes.data),
-                                None if ids is None else C.c_void_p(ids.ctypes.data), C.c_void_p(out.ctypes.data),
-                                C.byref(st)))
-        self.last_stats = st.as_dict()
+        self._call(lib().nori_gpu_li, C.byref(ld), C.c_void_p(rays.ctypes.data),
+                   None if ids is None else C.c_void_p(ids.ctypes.data), C.c_void_p(out.ctypes.data))
         return out
 
     def _splat_args(self, name, pos, val, n, out, variance):
         """(on_device, n, pos, val, film, variance addresses, the film to return) of a film splat:
         all numpy (host form) or all device addresses / torch tensors with a device film out=."""
-        def addr(a):
-            return int(a.data_ptr() if hasattr(a, "data_ptr") else a)
         host = [isinstance(a, np.ndarray) for a in (pos, val)]
         if any(host) != all(host):
             raise ValueError(f"{name}: pos and val must both be numpy arrays or both be device addresses")
@@ -836,22 +820,17 @@ class GpuRenderer:
                 if not hasattr(val, "numel"):
                     raise ValueError(f"{name}: int device addresses need the sample count")
                 n = val.numel() // 3
-            return 1, int(n), addr(pos), addr(val), addr(out), None if variance is None else addr(variance), None, ()
+            return 1, int(n), _addr(pos), _addr(val), _addr(out), _addr(variance), None, ()
         pos = np.ascontiguousarray(pos, dtype=np.float32).reshape(-1, 2)
         val = np.ascontiguousarray(val, dtype=np.float32).reshape(-1, 3)
         if pos.shape[0] != val.shape[0]:
             raise ValueError(f"{name}: {pos.shape[0]} positions and {val.shape[0]} values")
         if n is not None and int(n) != pos.shape[0]:
             raise ValueError(f"{name}: {pos.shape[0]} samples, expected {int(n)}")
-        if out is None:
-            out = np.zeros(self.scene.film_shape(), np.float32)
-        assert (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.flags.c_contiguous
-                and out.shape == self.scene.film_shape())
-        if variance is not None:
-            assert (isinstance(variance, np.ndarray) and variance.dtype == np.float32 and variance.flags.c_contiguous
-                    and variance.shape == (self.scene.height, self.scene.width, 8))
-        return (0, pos.shape[0], pos.ctypes.data, val.ctypes.data, out.ctypes.data,
-                None if variance is None else variance.ctypes.data, out, (pos, val))
+        assert out is None or isinstance(out, np.ndarray)
+        film, out = self._film_arg(out, None)
+        var = self._variance_arg(variance, False)
+        return 0, pos.shape[0], pos.ctypes.data, val.ctypes.data, film.value, var, out, (pos, val)
 
     def film_splat(self, pos, val, n=None, out=None, variance=None):
         """Samples anywhere on the image filtered into the film (nori_gpu_film_splat; the operation
@@ -864,9 +843,7 @@ class GpuRenderer:
         before the call.  last_stats: samples = splatted, invalid_samples = dropped, ms_splat."""
         dev, n, p, v, film, var, ret, keep = self._splat_args("film_splat", pos, val, n, out, variance)
         sd = _abi.SplatDesc(n, dev, 0, var)
-        st = _abi.Stats()
-        check(lib().nori_gpu_film_splat(self._h, C.byref(sd), C.c_void_p(p), C.c_void_p(v), C.c_void_p(film), C.byref(st)))
-        self.last_stats = st.as_dict()
+        self._call(lib().nori_gpu_film_splat, C.byref(sd), C.c_void_p(p), C.c_void_p(v), C.c_void_p(film))
         return ret
 
     def film_splat_passes(self, pos, val, passes=None, blocks=None, out=None, variance=None):
@@ -882,10 +859,7 @@ class GpuRenderer:
         dev, n, p, v, film, var, ret, keep = self._splat_args("film_splat_passes", pos, val, n, out, variance)
         rd.output_on_device = dev
         rd.variance_out = var
-        st = _abi.Stats()
-        check(lib().nori_gpu_film_splat_passes(self._h, C.byref(rd), C.c_void_p(p), C.c_void_p(v), C.c_void_p(film),
-                                               C.byref(st)))
-        self.last_stats = st.as_dict()
+        self._call(lib().nori_gpu_film_splat_passes, C.byref(rd), C.c_void_p(p), C.c_void_p(v), C.c_void_p(film))
         return ret
 
     def _vertex_arg(self, a, what):
