@@ -1,13 +1,14 @@
 // bsdf_desc.h -- nori_bsdf_desc -> DevBsdf on the host: the desc values and
 // the constants derived from them once per scene (the IOR quotients, ks,
-// Disney's alpha).  Shared by the scene upload (upload.hip) and the
+// Disney's alpha).  Shared by the scene plan (scene_plan.cpp) and the
 // test-only device library (devtest.hip), so the unit tests run the product's
 // derived constants.  Host code; compiled with -ffp-contract=off like the
 // rest, so every quotient rounds as the reference's per-call division does.
 #pragma once
 #include <cstring>
 
-#include "device_math.h"
+#include "../../include/nori_gpu.h"
+#include "dev_records.h"
 
 namespace nori {
 

@@ -15,6 +15,7 @@
 #include "comm.h"
 #include "kernels.h"
 #include "render_plan.h"
+#include "scene_plan.h"
 #include "scene_prep.h"
 
 #define HIP_TRY(x)                                                                                       \
@@ -177,10 +178,6 @@ struct nori_gpu_ctx {
         rb_scan, rb_inner, rb_leaf, rb_slots;
     hipEvent_t rb_ev[2] = {};
     std::vector<DevShape> hshapes;
-    struct EmitterMesh {
-        uint32_t shape, cdf_offset, vtx_first, vtx_count;  // the vertex range its triangles use
-        std::vector<uint32_t> tri;                          // 3 global vertex ids per triangle
-    };
     std::vector<EmitterMesh> emitter_meshes;
     uint32_t pool_cap = 0;
     uint32_t *pinned = nullptr;      // host-mapped flags: [0] done, [1] exhausted segments
@@ -298,7 +295,6 @@ struct FilmOut {
     }
 };
 
-int bvh_stack_for(uint32_t depth, int forced);                                                         // upload.hip
 void work_lists(nori_gpu_ctx &c, const nori_gpu_render_desc &rd);                                       // render.hip
 int render(nori_gpu_ctx &c, const nori_gpu_render_desc &rd, float *rgbw_out, nori_gpu_stats *stats);   // render.hip
 

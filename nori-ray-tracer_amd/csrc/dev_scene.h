@@ -26,40 +26,11 @@
 #endif
 #include <stdint.h>
 
+#include "dev_records.h"
 #include "device_math.h"
 #include "seg_index.h"
 
 namespace nori {
-
-struct DevShape {
-    int32_t type, bsdf, emitter, has_normals;
-    uint32_t prim_offset, prim_count, cdf_offset, has_uvs;
-    float center[3], radius;
-    float area_norm;     // DiscretePDF::getNormalization (mesh) or sphere pdf
-    int32_t nm_w, nm_h, nm_wrap;  // NormalMap (meshes with normals, mesh.cpp:147-155)
-    // sphere only: no other primitive meets the closed ball (host-checked with
-    // a margin, and the ball lies inside the scene box): a ray from a point of
-    // this sphere that hits it again hits nothing before (the chord is inside
-    // the ball), so the tail finisher takes that hit without a scene scan
-    int32_t solitary;
-    const uint32_t *nmap;         // RGBX8 texels in global memory, or null
-};
-
-// 128 B.  Area: radiance.  Envmap (envmap.cpp): R x C texels (R = Bitmap rows,
-// the reference's m_width), tables at float offsets into DevScene::env:
-// rgb R*C*3, pdf R*C, cdf R*(C+1), marginal pdf R, marginal cdf R+1.
-// Point (pointlight.cpp): position, power.  Spot (spotlight.cpp): position,
-// power (= "color"), direction, cosines of falloffStart and totalWidth.
-struct DevEmitter {
-    int32_t type, shape;
-    float radiance[3];
-    float weight;
-    int32_t R, C;
-    uint32_t rgb_off, pdf_off, cdf_off, pmarg_off, cmarg_off;
-    float position[3], power[3], direction[3], cos_fs, cos_tw;
-    uint32_t pad[8];
-};
-static_assert(sizeof(DevEmitter) == 128, "DevEmitter layout");
 
 struct DevScene {
     const float4 *nodes;

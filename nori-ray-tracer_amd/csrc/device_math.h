@@ -10,6 +10,8 @@
 #endif
 #include <stdint.h>
 
+#include "dev_records.h"
+
 // hipRTC writes the embedded headers into a temporary directory under their
 // names: a name with ../ in it would land outside that directory, in a place
 // shared with (and possibly owned by) other users, so the ABI header is
@@ -317,23 +319,7 @@ NHD float sq_gtr2_pdf(V3 m, float alpha) {  // warp.cpp:187-193
 // ---------------------------------------------------------------- BSDFs
 enum { kMeasureUnknown = 0, kMeasureSolidAngle = 1, kMeasureDiscrete = 2 };  // common.h:199-203
 
-// Device BSDF record: desc values plus derived constants.
-struct DevBsdf {
-    int32_t type;
-    float albedo[3];
-    float int_ior, ext_ior, alpha, ks;
-    float kd[3];
-    float base[3];
-    float metallic, specular, roughness, sheen, sheen_tint, spec_tint, d_alpha;
-    int32_t tex;  // diffuse albedo: NORI_TEXTURE_CONSTANT (albedo), _CHECKERBOARD (albedo = value1) or _IMAGE
-    float tex_v2[3], tex_delta[2], tex_scale[2];
-    int32_t img_w, img_h, img_wrap;  // NORI_TEXTURE_IMAGE: RGBX8 texels in global memory
-    const uint32_t *img;
-    // the IOR quotients fresnel() and Dielectric::sample compute per call,
-    // computed once on the host with the same float divisions:
-    // ext/int, int/ext and 1.0f / (ext/int)
-    float eta_ei, eta_ie, inv_eta_ei;
-};
+// (DevBsdf, the device BSDF record: dev_records.h)
 
 // ImageTexture::getData / NormalMap::getData (imagetexture.cpp:95-115): the
 // texel (int)(u W), (int)(v H), repeated (C++ %) or clamped.  eval's bilinear

@@ -139,8 +139,8 @@ struct Idct1D {
         t3 = p1 + p2 * f2f(0.765366865f);
         p2 = s0;
         p3 = s4;
-        t0 = (p2 + p3) << 12;
-        t1 = (p2 - p3) << 12;
+        t0 = (p2 + p3) * 4096;  // (stb's << 12; the sums can be negative)
+        t1 = (p2 - p3) * 4096;
         x0 = t0 + t3;
         x3 = t0 - t3;
         x1 = t1 + t2;
@@ -175,7 +175,7 @@ void idct_block(uint8_t *out, int stride, const short *d, const uint8_t *dq) {
         const uint8_t *q = dq + i;
         int *v = val + i;
         if (c[8] == 0 && c[16] == 0 && c[24] == 0 && c[32] == 0 && c[40] == 0 && c[48] == 0 && c[56] == 0) {
-            const int dc = c[0] * q[0] << 2;
+            const int dc = c[0] * q[0] * 4;  // (stb's << 2)
             for (int r = 0; r < 8; ++r) v[8 * r] = dc;
         } else {
             Idct1D k(c[0] * q[0], c[8] * q[8], c[16] * q[16], c[24] * q[24], c[32] * q[32], c[40] * q[40],

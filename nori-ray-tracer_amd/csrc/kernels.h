@@ -53,15 +53,7 @@ struct SplatDesc {
 
 // Scene-specialised scan kernels (rtc.hip): a scan-mode scene's scan list
 // compiled in as literals through hipRTC at context creation.
-struct ScanRtcScene {
-    const float *rec;  // 12 floats per record
-    uint32_t nrec;
-    const float *plane_c, *plane_f;  // per pair: 1 and 8 floats
-    uint32_t pairs;
-    uint32_t plane_end[3];
-    uint32_t tris, real;
-    float fast_max;  // the bound of scan.h's fast body (scene_prep.h scan_fast_max), 0: none
-};
+struct ScanRtcScene;  // scene_prep.h
 struct ScanRtc {
     hipModule_t mod = nullptr;
     hipFunction_t extend = nullptr, shadow = nullptr, trace[2] = {nullptr, nullptr};  // trace[any_hit]
@@ -111,7 +103,7 @@ hipError_t launch_shade(const DevScene &S, const PathQueue &in, const PathQueue 
 // The blob size up to which launch_shade stages the scene in LDS (the LDS
 // template argument, and the one the scene's ShadeRtc is compiled with).
 // The integrator k_shade is instantiated for (launch_shade's switch).
-inline int shade_integrator(int i) {
+constexpr int shade_integrator(int i) {
     return i == NORI_INTEGRATOR_PATH_MATS || i == NORI_INTEGRATOR_VOLUMETRIC ? i : (int)NORI_INTEGRATOR_PATH_MIS;
 }
 inline uint32_t shade_lds_bytes(uint32_t blob_bytes) { return blob_bytes <= kShadeLdsMax ? blob_bytes : 0u; }

@@ -1,5 +1,6 @@
 // scene_prep.cpp -- scene_prep.h's arithmetic and the C ABI's entry points
-// that need no device (include/nori_gpu.h: nori_scene_*, nori_film_*, ..).
+// that need no device (include/nori_gpu.h: nori_scene_*, nori_film_*, ..;
+// those that start from the scene's tree are in scene_plan.cpp).
 #include "scene_prep.h"
 
 #include <algorithm>
@@ -493,66 +494,6 @@ int nori_scene_load_xml(const char *path, int width, int height, int spp, nori_s
 }
 const nori_scene_desc *nori_scene_get_desc(const nori_scene *s) { return s ? &s->hs->desc : nullptr; }
 
-int nori_scene_bvh_info(const nori_scene_desc *d, nori_bvh_info *out) {
-    return guarded([&] {
-        if (!d || !out) return fail(NORI_ERR_INVALID, "null argument");
-        if (d->abi_version != NORI_GPU_ABI_VERSION) return fail(NORI_ERR_INVALID, "ABI version mismatch");
-        float rmin[3], rmax[3];
-        scene_root_box(*d, rmin, rmax);
-        DeviceBvh bvh;
-        build_device_bvh(*d, rmin, rmax, bvh);
-        std::memset(out, 0, sizeof(*out));
-        out->ref_nodes = bvh.ref_nodes;
-        out->device_nodes = bvh.num_nodes;
-        out->depth = bvh.depth;
-        out->num_prims = (uint32_t)(bvh.prims.size() / 12);
-        out->sah_cost = bvh.sah_cost;
-        uint64_t h = 1469598103934665603ull;
-        for (size_t i = 0; i < bvh.prims.size(); i += 12) {
-            uint32_t id;
-            std::memcpy(&id, &bvh.prims[i + 3], 4);
-            for (int k = 0; k < 4; ++k) h = (h ^ ((id >> (8 * k)) & 0xFFu)) * 1099511628211ull;
-        }
-        out->order_hash = h;
-        return NORI_OK;
-    });
-}
-int nori_scene_scan_list(const nori_scene_desc *d, nori_scan_info *info, float *records, float *plane_c,
-                         float *plane_f) {
-    return guarded([&] {
-        if (!d || !info) return fail(NORI_ERR_INVALID, "null argument");
-        if (d->abi_version != NORI_GPU_ABI_VERSION) return fail(NORI_ERR_INVALID, "ABI version mismatch");
-        float rmin[3], rmax[3];
-        scene_root_box(*d, rmin, rmax);
-        DeviceBvh bvh;
-        build_device_bvh(*d, rmin, rmax, bvh);
-        const uint32_t n = (uint32_t)(bvh.prims.size() / 12);
-        std::memset(info, 0, sizeof(*info));
-        if (n > kScanMaxPrims) return NORI_OK;  // a BVH scene: no scan list
-        const ScanList L = build_scan_list(bvh, n);
-        info->records = (uint32_t)(L.prims.size() / 12);
-        info->pairs = (uint32_t)L.plane_c.size();
-        for (int a = 0; a < 3; ++a) info->plane_end[a] = L.plane_end[a];
-        info->tris = L.tris;
-        if (records) std::memcpy(records, L.prims.data(), L.prims.size() * 4);
-        if (plane_c && !L.plane_c.empty()) std::memcpy(plane_c, L.plane_c.data(), L.plane_c.size() * 4);
-        if (plane_f && !L.plane_f.empty()) std::memcpy(plane_f, L.plane_f.data(), L.plane_f.size() * 4);
-        return NORI_OK;
-    });
-}
-int nori_scene_scan_fast(const nori_scene_desc *d, float *fast_max) {
-    return guarded([&] {
-        if (!d || !fast_max) return fail(NORI_ERR_INVALID, "null argument");
-        if (d->abi_version != NORI_GPU_ABI_VERSION) return fail(NORI_ERR_INVALID, "ABI version mismatch");
-        float rmin[3], rmax[3];
-        scene_root_box(*d, rmin, rmax);
-        DeviceBvh bvh;
-        build_device_bvh(*d, rmin, rmax, bvh);
-        const uint32_t n = (uint32_t)(bvh.prims.size() / 12);
-        *fast_max = n > kScanMaxPrims ? 0.0f : build_scan_list(bvh, n).fast_max;
-        return NORI_OK;
-    });
-}
 void nori_scene_free(nori_scene *s) { delete s; }
 
 int nori_film_border(const nori_scene_desc *d) { return d ? film_border(d->camera) : NORI_ERR_INVALID; }
@@ -571,25 +512,6 @@ int nori_film_develop(const nori_scene_desc *d, const float *rgbw, float *rgb) {
             for (int k = 0; k < 3; ++k) o[k] = c[3] != 0 ? c[k] / c[3] : 0.0f;  // color.h:113-118
         }
     return NORI_OK;
-}
-
-int nori_scene_bvh_refit(const nori_scene_desc *d, const float *positions, float *nodes, float *prims, float *root_box) {
-    return guarded([&] {
-        if (!d) return fail(NORI_ERR_INVALID, "null argument");
-        if (d->abi_version != NORI_GPU_ABI_VERSION) return fail(NORI_ERR_INVALID, "ABI version mismatch");
-        if (positions)
-            for (size_t i = 0; i < 3 * (size_t)d->num_vertices; ++i)
-                if (!std::isfinite(positions[i])) return fail(NORI_ERR_INVALID, "nori_scene_bvh_refit: a non-finite position");
-        float rmin[3], rmax[3];
-        scene_root_box(*d, rmin, rmax);
-        DeviceBvh bvh;
-        build_device_bvh(*d, rmin, rmax, bvh);
-        if (positions) refit_host(bvh, build_refit_plan(bvh), prim_vertex_ids(*d), positions, nullptr);
-        if (nodes) std::memcpy(nodes, bvh.nodes.data(), bvh.nodes.size() * 4);
-        if (prims) std::memcpy(prims, bvh.prims.data(), bvh.prims.size() * 4);
-        if (root_box) refit_root_box(bvh.nodes.data(), root_box);
-        return NORI_OK;
-    });
 }
 
 int nori_scene_bvh_rebuild(const nori_scene_desc *d, const float *positions, uint32_t leaf_max,

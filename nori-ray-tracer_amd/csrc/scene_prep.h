@@ -90,6 +90,17 @@ struct ScanList {
     float fast_max = 0.0f;      // scan_fast_max of this list
 };
 ScanList build_scan_list(const DeviceBvh &bvh, uint32_t n);
+// A scan list as the scene-specialised kernels take it (rtc.hip compiles it
+// in as literals through hipRTC; kernels.h)
+struct ScanRtcScene {
+    const float *rec;  // 12 floats per record
+    uint32_t nrec;
+    const float *plane_c, *plane_f;  // per pair: 1 and 8 floats
+    uint32_t pairs;
+    uint32_t plane_end[3];
+    uint32_t tris, real;
+    float fast_max;  // the bound of scan.h's fast body (scan_fast_max), 0: none
+};
 // The bound M of the scene-specialised scan's fast body (scan.h): a ray whose
 // origin and direction components are all at most M in magnitude keeps every
 // intermediate of the triangle tests of this list -- tvec, pvec, qvec, det and

@@ -32,7 +32,7 @@ from test_bvh_build import _compare
 from test_gpu_parity import _compare_hits, _rays
 
 PILES = [64, 65, 128, 129, 200, 1000]
-# 4-wide depth bands (upload.hip bvh_stack_for: need = 3 * depth + 1 entries; 4, 8 or 16 of
+# 4-wide depth bands (scene_plan.cpp bvh_stack_for: need = 3 * depth + 1 entries; 4, 8 or 16 of
 # them in LDS for stack 8, 16, 32 and 64 more in private memory)
 BANDS = {"d22": (1, 22), "d23": (23, 23), "d24": (24, 26), "d26": (24, 26), "d27": (27, 64)}
 

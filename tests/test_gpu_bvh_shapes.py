@@ -4,7 +4,7 @@ other, reference leaves larger than the device's 64-primitive leaves, the scan/B
 kernel that walks the tree at stack 32, and the refusal of a tree no stack can hold.
 
 The scenes are bvh_shapes.py's (their builds, depths and the comparison's tie rule are checked on
-the CPU in test_bvh_shapes.py).  The stack follows from the depth (upload.hip bvh_stack_for:
+the CPU in test_bvh_shapes.py).  The stack follows from the depth (scene_plan.cpp bvh_stack_for:
 3 * depth + 1 entries needed; stack 8, 16, 32 keep 4, 8, 16 of them in LDS and 64 in private
 memory) or from NORI_BVH_STACK, read at context creation; there is no stats field for it.
 

@@ -215,7 +215,7 @@ def test_rays_equal_a_fresh_context(cases, which, pset):
 
 def test_every_stack_that_accepts_the_deepest_tree(cases):
     """nest d26 needs 3 * 26 + 1 = 79 stack entries; NORI_BVH_STACK = 8, 16, 32 hold 4, 8, 16 in
-    LDS and 64 more in private memory (upload.hip bvh_stack_for), so only 32 accepts it."""
+    LDS and 64 more in private memory (scene_plan.cpp bvh_stack_for), so only 32 accepts it."""
     s, P = cases.scene("nest"), cases.positions("nest", "b")
     need = 3 * nori_amd.bvh_info(s)["depth"] + 1
     accepted = [k for k in (8, 16, 32) if need <= k // 2 + 64]

@@ -18,7 +18,7 @@ import synth
 from conftest import ROOT, scene_path
 
 CSRC = os.path.join(ROOT, "nori-ray-tracer_amd", "csrc")
-UNITS = ["scene_prep.cpp", "shard.cpp", "scene_loader.cpp", "bvh_builder.cpp", "bvh_refit.cpp", "bvh_rebuild.cpp",
+UNITS = ["scene_prep.cpp", "scene_plan.cpp", "shard.cpp", "scene_loader.cpp", "bvh_builder.cpp", "bvh_refit.cpp", "bvh_rebuild.cpp",
          "image_decode.cpp", "image_io.cpp"]
 SCENES = [("pa4", "cbox", "cbox_path_mis.xml"), ("pa3", "odyssey", "odyssey_mis.xml"), ("pa3", "veach_mi", "veach_mis.xml")]
 
