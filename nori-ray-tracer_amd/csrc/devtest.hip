@@ -1,15 +1,27 @@
-// devtest.hip -- libnori_devtest.so: the device routines of device_math.h and
-// shading.h behind plain C entry points, for the unit tests
-// (tests/test_gpu_device_units.py, tests/devtest_util.py).  Not part of
-// libnori_gpu.so.  Every kernel is element-wise: one thread per element,
-// guarded by i < n, no shared state.  Every entry point takes host arrays,
-// allocates, copies, launches, copies back and returns the HIP status.
+// devtest.hip -- libnori_devtest.so: device routines behind plain C entry
+// points, for the unit tests (tests/devtest_util.py).  Not part of
+// libnori_gpu.so.  Covered:
+//  - device_math.h and shading.h (tests/test_gpu_device_units.py): the
+//    correctly rounded and fast math forms, pcg_skip3, the BSDFs, the
+//    glass-sphere chain;
+//  - the tail finisher's pieces (tests/test_gpu_finish_tail.py): the body of
+//    k_tail_prefix (coop_scan.h), the gid -> segment -> queue-slot lookup
+//    (tail_index.h), coop_load / coop_scan (coop_scan.h);
+//  - the scan's primitive tests (scan.h): tri_hit, tri_hit_nb,
+//    tri_hit_plane<A>, sphere_hit, sphere_hit_nb, sphere_hit_fast, box_test.
+// Every kernel but the first and third of the finisher group is element-wise:
+// one thread per element, guarded by i < n, no shared state; those two run
+// whole work-groups (the prefix) or whole waves (the cooperative scan) as the
+// finisher does.  Every entry point takes host arrays, allocates, copies,
+// launches, copies back and returns the HIP status.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "bsdf_desc.h"
+#include "coop_scan.h"
 #include "kernels.h"
 #include "shading.h"
+#include "tail_index.h"
 
 using namespace nori;
 
@@ -228,6 +240,101 @@ __global__ void k_glass(DevShape sh, DevBsdf B, uint64_t seed, const float *o, c
     w[0] = flags;
 }
 
+// ------------------------------------------------------------------ tail finisher
+__global__ __launch_bounds__(1024) void k_dt_tail_prefix(const uint32_t *cnt, uint32_t G, uint32_t *pre) {
+    tail_prefix(cnt, G, pre);
+}
+
+// The outputs are stored, never used as addresses.
+__global__ void k_dt_tail_lookup(const uint32_t *pre, uint32_t G, const uint32_t *gids, uint32_t n, uint32_t *seg_out,
+                                 uint32_t *slot_out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t gid = gids[i], sg = tail_segment(pre, G, gid);
+    seg_out[i] = sg;
+    slot_out[i] = tail_slot(pre, sg, gid);
+}
+
+__device__ inline TRay load_ray(const float *rays, uint32_t i) {
+    const float *p = rays + 8 * (size_t)i;
+    return TRay{V3{p[0], p[1], p[2]}, V3{p[4], p[5], p[6]}, V3{0, 0, 0}, p[3], p[7]};
+}
+
+// Whole waves: the grid covers n rounded up to work-groups of kTraceBlock and
+// no thread returns before the scan, so all 64 lanes of every wave reach
+// coop_load and coop_scan converged (its precondition); the lanes past n do
+// not want a ray.
+template <bool ANY>
+__global__ __launch_bounds__(kTraceBlock) void k_dt_coop_scan(DevScene S, const float *rays, const uint8_t *want, uint32_t n,
+                                                              uint32_t *out) {
+    const uint32_t i = blockIdx.x * kTraceBlock + threadIdx.x;
+    const bool in = i < n;
+    TRay r{V3{0, 0, 0}, V3{0, 0, 0}, V3{0, 0, 0}, 0.0f, 0.0f};
+    bool w = false;
+    if (in) {
+        r = load_ray(rays, i);
+        w = want[i] != 0;
+    }
+    const CoopPrim cp = coop_load(S);
+    float t, u, v;
+    uint32_t p;
+    const bool res = coop_scan<ANY>(S, cp, r, w, t, p, u, v);
+    if (in) {
+        uint32_t *o = out + 5 * (size_t)i;
+        o[0] = res ? 1u : 0u;
+        o[1] = __float_as_uint(t);
+        o[2] = p;
+        o[3] = __float_as_uint(u);
+        o[4] = __float_as_uint(v);
+    }
+}
+
+// ------------------------------------------------------------------ primitive tests
+enum {
+    kFormTri = 0,
+    kFormTriNb = 1,
+    kFormTriPlane0 = 2,
+    kFormTriPlane1 = 3,
+    kFormTriPlane2 = 4,
+    kFormSphere = 5,
+    kFormSphereNb = 6,
+    kFormSphereFast = 7,
+    kFormSphereFastNocheck = 8,
+    kFormBox = 9,
+    kFormCount = 10
+};
+
+// Ray i against record i (three float4); mint and maxt as given.  out: 4
+// words per element, (hit, t, u, v); for the box (record: min, max, unused)
+// (ok, tnear, 0, 0) with the ray's rcp computed as the scan prologue does.
+template <int FORM>
+__global__ void k_dt_prim_hit(const float4 *rec, const float *rays, uint32_t n, uint32_t *out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float4 a = rec[3 * (size_t)i], b = rec[3 * (size_t)i + 1], c = rec[3 * (size_t)i + 2];
+    TRay r = load_ray(rays, i);
+    float t = 0.0f, u = 0.0f, v = 0.0f;
+    bool h;
+    if constexpr (FORM == kFormTri) h = tri_hit(a, b, c, r, t, u, v);
+    else if constexpr (FORM == kFormTriNb) h = tri_hit_nb(a, b, c, r, t, u, v);
+    else if constexpr (FORM == kFormTriPlane0) h = tri_hit_plane<0>(a, b, c, r, t, u, v);
+    else if constexpr (FORM == kFormTriPlane1) h = tri_hit_plane<1>(a, b, c, r, t, u, v);
+    else if constexpr (FORM == kFormTriPlane2) h = tri_hit_plane<2>(a, b, c, r, t, u, v);
+    else if constexpr (FORM == kFormSphere) h = sphere_hit(a, b, r, t);
+    else if constexpr (FORM == kFormSphereNb) h = sphere_hit_nb<false>(a, b, r, t);
+    else if constexpr (FORM == kFormSphereFast) h = sphere_hit_fast<false>(a, b, r, t);
+    else if constexpr (FORM == kFormSphereFastNocheck) h = sphere_hit_fast<true>(a, b, r, t);
+    else {
+        r.rcp = V3{rcp_full(r.d.x), rcp_full(r.d.y), rcp_full(r.d.z)};
+        h = box_test(a, b, r, t);
+    }
+    uint32_t *o = out + 4 * (size_t)i;
+    o[0] = h ? 1u : 0u;
+    o[1] = __float_as_uint(t);
+    o[2] = __float_as_uint(u);
+    o[3] = __float_as_uint(v);
+}
+
 }  // namespace
 
 extern "C" {
@@ -340,6 +447,77 @@ __attribute__((visibility("default"))) int nori_devtest_glass(int integrator, co
         hipLaunchKernelGGL(k_glass<NORI_INTEGRATOR_PATH_MATS>, dim3(grid(n)), dim3(kBlock), 0, 0, sh, b, seed, dor, dd,
                            db, n, dout);
     return buf.back(out, dout, (size_t)kGlassWords * n);
+}
+
+// pre_out[0 .. G]: the exclusive prefix of cnt[0 .. G) and its total, by the
+// body of k_tail_prefix launched as launch_tail_prefix does (1 x 1024).
+__attribute__((visibility("default"))) int nori_devtest_tail_prefix(const uint32_t *cnt, uint32_t G, uint32_t *pre_out) {
+    if (!cnt || !pre_out || G == 0) return hipErrorInvalidValue;
+    Buffers buf;
+    const uint32_t *dcnt = buf.in(cnt, (size_t)G);
+    uint32_t *dpre = buf.out<uint32_t>((size_t)G + 1);
+    if (buf.err != hipSuccess) return buf.err;
+    hipLaunchKernelGGL(k_dt_tail_prefix, dim3(1), dim3(1024), 0, 0, dcnt, G, dpre);
+    return buf.back(pre_out, dpre, (size_t)G + 1);
+}
+
+// seg_out[i] = tail_segment(pre, G, gids[i]), slot_out[i] = tail_slot of it; pre has G + 1 entries.
+__attribute__((visibility("default"))) int nori_devtest_tail_lookup(const uint32_t *pre, uint32_t G, const uint32_t *gids,
+                                                                     uint32_t n, uint32_t *seg_out, uint32_t *slot_out) {
+    if (!pre || !gids || !seg_out || !slot_out || G == 0) return hipErrorInvalidValue;
+    Buffers buf;
+    const uint32_t *dpre = buf.in(pre, (size_t)G + 1), *dg = buf.in(gids, (size_t)n);
+    uint32_t *dseg = buf.out<uint32_t>((size_t)n), *dslot = buf.out<uint32_t>((size_t)n);
+    if (buf.err != hipSuccess) return buf.err;
+    hipLaunchKernelGGL(k_dt_tail_lookup, dim3(grid(n)), dim3(kBlock), 0, 0, dpre, G, dg, n, dseg, dslot);
+    const hipError_t e = buf.back(seg_out, dseg, (size_t)n);
+    return e != hipSuccess ? e : buf.back(slot_out, dslot, (size_t)n);
+}
+
+// coop_load + coop_scan<any_hit> of n rays (8 floats: o, mint, d, maxt) over
+// the np <= 64 records (3 float4 each), lanes with want[i] == 0 not tracing.
+// out: n x 5 words (res, t, prim, u, v), of every lane.
+__attribute__((visibility("default"))) int nori_devtest_coop_scan(const float *records, uint32_t np, const float *root_min,
+                                                                   const float *root_max, const float *rays,
+                                                                   const uint8_t *want, uint32_t n, int any_hit,
+                                                                   uint32_t *out) {
+    if (!records || !root_min || !root_max || !rays || !want || !out || np > 64) return hipErrorInvalidValue;
+    Buffers buf;
+    const float *drec = buf.in(records, 12 * (size_t)np), *dr = buf.in(rays, 8 * (size_t)n);
+    const uint8_t *dw = buf.in(want, (size_t)n);
+    uint32_t *dout = buf.out<uint32_t>(5 * (size_t)n);
+    if (buf.err != hipSuccess) return buf.err;
+    DevScene S;  // only what coop_load / coop_scan read
+    std::memset(&S, 0, sizeof(S));
+    S.prims = reinterpret_cast<const float4 *>(drec);
+    S.num_prims = np;
+    for (int k = 0; k < 3; ++k) S.root_min[k] = root_min[k], S.root_max[k] = root_max[k];
+    const dim3 g(n ? (n + kTraceBlock - 1) / kTraceBlock : 1), b(kTraceBlock);
+    if (any_hit) hipLaunchKernelGGL(k_dt_coop_scan<true>, g, b, 0, 0, S, dr, dw, n, dout);
+    else hipLaunchKernelGGL(k_dt_coop_scan<false>, g, b, 0, 0, S, dr, dw, n, dout);
+    return buf.back(out, dout, 5 * (size_t)n);
+}
+
+__attribute__((visibility("default"))) int nori_devtest_prim_forms(void) { return kFormCount; }
+
+// Ray i (8 floats: o, mint, d, maxt) against record i (12 floats) with the
+// test `form`; out: n x 4 words (k_dt_prim_hit).
+__attribute__((visibility("default"))) int nori_devtest_prim_hit(int form, const float *records, const float *rays,
+                                                                  uint32_t n, uint32_t *out) {
+    if (form < 0 || form >= kFormCount || !records || !rays || !out) return hipErrorInvalidValue;
+    Buffers buf;
+    const float4 *drec = reinterpret_cast<const float4 *>(buf.in(records, 12 * (size_t)n));
+    const float *dr = buf.in(rays, 8 * (size_t)n);
+    uint32_t *dout = buf.out<uint32_t>(4 * (size_t)n);
+    if (buf.err != hipSuccess) return buf.err;
+    switch (form) {
+#define NORI_FORM(k) \
+    case k: hipLaunchKernelGGL(k_dt_prim_hit<k>, dim3(grid(n)), dim3(kBlock), 0, 0, drec, dr, n, dout); break;
+        NORI_FORM(0) NORI_FORM(1) NORI_FORM(2) NORI_FORM(3) NORI_FORM(4) NORI_FORM(5) NORI_FORM(6) NORI_FORM(7)
+        NORI_FORM(8) NORI_FORM(9)
+#undef NORI_FORM
+    }
+    return buf.back(out, dout, 4 * (size_t)n);
 }
 
 }  // extern "C"

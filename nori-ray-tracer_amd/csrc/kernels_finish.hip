@@ -1,12 +1,21 @@
 // kernels_finish.hip -- the tail of a chunk: k_mark, k_tail_prefix and
 // k_finish, which runs every path still queued to completion and splats its
-// sample itself; the cooperative scan only the finisher uses; their launchers.
+// sample itself; their launchers.  The cooperative scan only the finisher
+// uses and the prefix's body are in coop_scan.h, the numbering of the queued
+// paths in tail_index.h.
 #include <algorithm>
 
+#include "coop_scan.h"
 #include "shading.h"
+#include "tail_index.h"
 #include "traverse.h"
 
 namespace nori {
+
+// k_mark and the finisher's grid run two work-groups of kTraceBlock threads
+// per segment, in whole waves.
+static_assert(kSeg == 2 * kTraceBlock, "k_mark and the 2 * G grid of k_finish: two work-groups per segment");
+static_assert(kTraceBlock % 64 == 0, "k_finish numbers its paths per wave");
 
 // Pending marker for the samples the finisher will splat itself.
 __global__ __launch_bounds__(kTraceBlock) void k_mark(PathQueue Q, SegState seg, int sel, float4 *rec) {
@@ -15,120 +24,9 @@ __global__ __launch_bounds__(kTraceBlock) void k_mark(PathQueue Q, SegState seg,
     rec[__float_as_uint(Q.ray_d[sg * kSeg + idx].w) & kWorkMask].w = __uint_as_float(kRecPending);
 }
 
-// Cooperative scan (scan-mode scenes, n <= 64 primitives): the rays of the
-// lanes in `want` are traced one after another by the whole wave, lane l
-// testing primitive l against the broadcast ray.  The result is exactly that
-// of traverse<0, ANY> for the ray: every candidate passes the test against the
-// ray's own maxt, the closest wins, and among equal t the last primitive in
-// scan order wins (the `t <= maxt` update).  A lone tail path then pays one
-// primitive test per ray instead of n.
-struct CoopPrim {  // lane l's primitive, loaded once per finisher wave
-    float4 p0, p1, p2;  // p2.w: leaf-order position (the tie rule of scan_core)
-    bool has, tri;
-};
-ND CoopPrim coop_load(const DevScene &S) {
-    CoopPrim c;
-    const uint32_t lane = lane_id();
-    c.has = lane < S.num_prims;
-    c.p0 = c.p1 = c.p2 = make_float4(0, 0, 0, 0);
-    if (c.has) {
-        const float4 *pp = S.prims + 3 * (size_t)lane;
-        c.p0 = pp[0];
-        c.p1 = pp[1];
-        c.p2 = pp[2];
-    }
-    c.tri = __float_as_uint(c.p1.w) == 0u;
-    return c;
-}
-template <bool ANY>
-ND bool coop_scan(const DevScene &S, const CoopPrim &cp, const TRay &mine, bool want, float &t, uint32_t &p, float &u,
-                  float &v) {
-    const uint32_t lane = lane_id();
-    const float4 rmn = make_float4(S.root_min[0], S.root_min[1], S.root_min[2], 0.f);
-    const float4 rmx = make_float4(S.root_max[0], S.root_max[1], S.root_max[2], 0.f);
-    bool res = false;
-    t = INF_F;
-    p = 0xFFFFFFFFu;
-    u = v = 0.0f;
-    auto bcast = [](float x, int j) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), j)); };
-    uint64_t m = __ballot(want);
-    while (m) {
-        const int j = __builtin_ctzll(m);
-        m &= m - 1;
-        TRay r;
-        r.o = V3{bcast(mine.o.x, j), bcast(mine.o.y, j), bcast(mine.o.z, j)};
-        r.d = V3{bcast(mine.d.x, j), bcast(mine.d.y, j), bcast(mine.d.z, j)};
-        r.mint = bcast(mine.mint, j);
-        r.maxt = bcast(mine.maxt, j);
-        if (r.mint == kEps) r.mint = smax(r.mint, r.mint * smax(smax(fabsf(r.o.x), fabsf(r.o.y)), fabsf(r.o.z)));
-        r.rcp = V3{rcp_full(r.d.x), rcp_full(r.d.y), rcp_full(r.d.z)};
-        float tn;
-        const bool live = !(r.maxt < r.mint) && box_test(rmn, rmx, r, tn);
-        float tl = 0, ul = 0, vl = 0;
-        bool hl = false;
-        if (cp.has) hl = cp.tri ? tri_hit_nb(cp.p0, cp.p1, cp.p2, r, tl, ul, vl) : sphere_hit_nb(cp.p0, cp.p1, r, tl);
-        uint64_t hm = __ballot(hl && live);
-        if (ANY) {
-            if ((int)lane == j) res = hm != 0ull;
-            continue;
-        }
-        if (!hm) continue;
-        // closest hit over the (few) hitting lanes, the later leaf-order
-        // position among equal t (scan_core's rule); t > 0, so its bits order
-        // like the value and the comparison stays scalar
-        uint32_t best = 0xFFFFFFFFu, best_pos = 0;
-        int w = 0;
-        do {
-            const int l = __builtin_ctzll(hm);
-            hm &= hm - 1;
-            const uint32_t tb = (uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(tl + 0.0f), l);
-            const uint32_t pos = (uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(cp.p2.w), l);
-            if (tb < best || (tb == best && pos >= best_pos)) {
-                best = tb;
-                best_pos = pos;
-                w = l;
-            }
-        } while (hm);
-        const float tw = __uint_as_float(best), uw = bcast(cp.tri ? ul : 0.0f, w), vw = bcast(cp.tri ? vl : 0.0f, w);
-        const uint32_t pw = (uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(cp.p0.w), w);
-        if ((int)lane == j) {
-            res = true;
-            t = tw;
-            p = pw;
-            u = uw;
-            v = vw;
-        }
-    }
-    return res;
-}
-
-// At most this many tracing lanes use the cooperative scan (each costs one
-// primitive test per lane and a reduction; the per-lane scan costs n tests).
-#ifndef NORI_COOP_MAX
-#define NORI_COOP_MAX 4
-#endif
-constexpr int kCoopMax = NORI_COOP_MAX;
-
 // Exclusive prefix of the queued-path counts of the G segments (pre[G] = total).
 __global__ __launch_bounds__(1024) void k_tail_prefix(const uint32_t *cnt, uint32_t G, uint32_t *pre) {
-    __shared__ uint32_t part[1024];
-    const uint32_t t = threadIdx.x, per = (G + 1023) / 1024, b = t * per, e = min(G, b + per);
-    uint32_t sum = 0;
-    for (uint32_t i = b; i < e; ++i) sum += cnt[i];
-    part[t] = sum;
-    __syncthreads();
-    for (uint32_t off = 1; off < 1024; off <<= 1) {  // inclusive scan (Hillis-Steele)
-        const uint32_t v = t >= off ? part[t - off] : 0u;
-        __syncthreads();
-        part[t] += v;
-        __syncthreads();
-    }
-    uint32_t run = t ? part[t - 1] : 0u;
-    for (uint32_t i = b; i < e; ++i) {
-        pre[i] = run;
-        run += cnt[i];
-    }
-    if (t == 1023) pre[G] = part[1023];
+    tail_prefix(cnt, G, pre);
 }
 
 // Runs every path still queued to completion, one thread per path: the
@@ -138,15 +36,6 @@ __global__ __launch_bounds__(1024) void k_tail_prefix(const uint32_t *cnt, uint3
 #ifndef NORI_FINISH_PRIO
 #define NORI_FINISH_PRIO 1
 #endif
-#ifndef NORI_FINISH_WAVES  // 0: 64 paths per wave
-// 2048 since the glass-sphere chain (round 3): fewer finisher waves leave the
-// film splat beside it more of the chip; 64-spp share 3446 -> 3550 (4096) ->
-// 3652 (2048) Msamples/s, 512 spp 4737 -> 4753 / 4744 (one box, interleaved).
-// 1024 since round 6's shorter glass chain: 64-spp share 4677 -> 4725 (4
-// reps, every 1024 run above every 2048 run), 512 spp 5843 / 5834 (noise)
-#define NORI_FINISH_WAVES 1024
-#endif
-constexpr uint32_t kFinishWaves = NORI_FINISH_WAVES;
 #ifndef NORI_FINISH_GLASS  // 0: the tail finisher shades glass-sphere vertices generically
 #define NORI_FINISH_GLASS 1
 #endif
@@ -165,8 +54,8 @@ __global__ __launch_bounds__(kTraceBlock) void k_finish(DevScene Sg, PathQueue Q
     // close to the lone-lane latency from its first bounce on.
     constexpr bool FULL = VAR != 0, CHROMA = VAR == 2;
     const uint32_t n = pre[G];
-    const uint32_t K = kFinishWaves ? min(64u, max(1u, (n + kFinishWaves - 1) / kFinishWaves)) : 64u;
-    if (blockIdx.x * (kTraceBlock / 64) * K >= n) return;  // whole block idle
+    const uint32_t K = tail_paths_per_wave(n);
+    if (tail_block_first(blockIdx.x, kTraceBlock / 64, K) >= n) return;  // whole block idle
     // Each bounce of a tail path is a chain of dependent reads of small
     // tables; for small scenes they are staged into LDS first so the chain
     // runs at LDS latency instead of L2 latency.
@@ -176,7 +65,7 @@ __global__ __launch_bounds__(kTraceBlock) void k_finish(DevScene Sg, PathQueue Q
         __syncthreads();
         S = scene_in_lds(Sg, reinterpret_cast<const char *>(blob_lds));
     }
-    const uint32_t first = (blockIdx.x * kTraceBlock + threadIdx.x) / 64 * K, gid = first + lane_id();
+    const uint32_t first = tail_first(blockIdx.x * kTraceBlock + threadIdx.x, K), gid = first + lane_id();
     if (first >= n) return;  // whole wave idle
 #if NORI_FINISH_PRIO
     // the film splat runs beside the finisher: its waves must not take the
@@ -185,16 +74,8 @@ __global__ __launch_bounds__(kTraceBlock) void k_finish(DevScene Sg, PathQueue Q
 #endif
     bool active = lane_id() < K && gid < n;
     uint32_t sg = 0;
-    if (active) {  // segment of path gid: last s with pre[s] <= gid
-        uint32_t lo = 0, hi = G;
-        while (hi - lo > 1) {
-            const uint32_t mid = (lo + hi) >> 1;
-            if (pre[mid] <= gid) lo = mid;
-            else hi = mid;
-        }
-        sg = lo;
-    }
-    const uint32_t q = sg * kSeg + (active ? gid - pre[sg] : 0u);
+    if (active) sg = tail_segment(pre, G, gid);  // last s with pre[s] <= gid
+    const uint32_t q = active ? tail_slot(pre, sg, gid) : 0u;  // (sg = 0 for an idle lane)
     PathState ps;
     float4 h = make_float4(0, 0, 0, 0);
     if (active) {
@@ -362,7 +243,7 @@ static void finish_dispatch(const DevScene &S, const PathQueue &Q, const SegStat
     // enough waves for any path count n <= 256 G (kFinishWaves, or n / 64 <= 4 G when
     // K = 64); the idle blocks exit at once
     constexpr uint32_t wpb = kTraceBlock / 64;  // waves per block
-    dim3 g(std::max<uint32_t>(2 * G, (kFinishWaves + wpb - 1) / wpb)), b(kTraceBlock);
+    dim3 g(tail_grid(G, wpb)), b(kTraceBlock);
     with_stack<0, 64>(stack, [&](auto N) {
         if constexpr (N() == 0) {  // LDS-staged when the scene has a blob
             if (S.blob_bytes) {

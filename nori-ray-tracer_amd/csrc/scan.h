@@ -116,9 +116,13 @@ ND bool tri_hit_nb(const float4 &a, const float4 &b, const float4 &c, const TRay
 // zeros are left out.  In cross() and dot() each of them only ever adds a
 // signed zero to, or subtracts one from, a single other product, so every
 // intermediate keeps its value; only the sign of an exactly zero result can
-// differ, which no acceptance test sees (t = +-0 < mint; u = +-0 and v = +-0
-// compare alike), so hits and t are bit-identical and u, v equal as values.
-// 12 of the test's ~65 VALU instructions fewer.
+// differ, which no acceptance test sees (u = +-0 and v = +-0 compare alike,
+// t = +-0 against mint too), so the hits are the same, u, v equal as values,
+// and t bit-identical for every ray with mint > 0 (t = +-0 < mint is never
+// accepted).  A ray with mint <= 0 and its origin in the plane is accepted at
+// t = +-0, and there the two forms' zeros differ in sign (tests/
+// test_gpu_finish_tail.py pins it): scan_core's ZMINT sends such rays to the
+// generic test.  12 of the test's ~65 VALU instructions fewer.
 template <int A>
 ND bool tri_hit_plane(const float4 &a, const float4 &b, const float4 &c, const TRay &r, float &t, float &u,
                       float &v) {

@@ -1,7 +1,8 @@
 """ctypes loader of libnori_devtest.so (nori-ray-tracer_amd/csrc/devtest.hip):
-the device routines of device_math.h and shading.h as element-wise kernels
-behind C entry points, with thin numpy wrappers.  No assertions here; a HIP
-error raises RuntimeError."""
+the device routines of device_math.h and shading.h, the pieces of the tail
+finisher (coop_scan.h, tail_index.h) and the primitive tests of scan.h behind
+C entry points, with thin numpy wrappers.  No assertions here; a HIP error
+raises RuntimeError."""
 import ctypes as C
 import os
 
@@ -16,6 +17,10 @@ LIB_PATH = os.path.join(ROOT, "nori-ray-tracer_amd", "lib", "libnori_devtest.so"
 SQRT_RN, RCP_RN, RCP_FULL, FSQRT_FAST, FSQRT_IEEE = 0, 1, 2, 3, 4
 NORMALIZE_FAST, NORMALIZE_IEEE, FRAME_FAST, FRAME_IEEE = 5, 6, 7, 8
 FRESNEL_FAST, FRESNEL_IEEE, TAN_THETA = 9, 10, 11
+
+# forms of nori_devtest_prim_hit (devtest.hip)
+TRI, TRI_NB, TRI_PLANE0, TRI_PLANE1, TRI_PLANE2 = 0, 1, 2, 3, 4
+SPHERE, SPHERE_NB, SPHERE_FAST, SPHERE_FAST_NOCHECK, BOX = 5, 6, 7, 8, 9
 
 # flags word of a glass lane
 GLASS_CHORD, GLASS_STEP, GLASS_ALIVE, GLASS_HIT = 1, 2, 4, 8
@@ -37,6 +42,12 @@ def lib():
         l.nori_devtest_bsdf_eval_pdf.argtypes = [pd, C.c_int, pf, pf, pf, u32, pf]
         l.nori_devtest_glass_words.argtypes = []
         l.nori_devtest_glass.argtypes = [C.c_int, pf, C.c_float, pd, C.c_uint64, pf, pf, pf, u32, C.POINTER(u32)]
+        pu32, pu8 = C.POINTER(u32), C.POINTER(C.c_uint8)
+        l.nori_devtest_tail_prefix.argtypes = [pu32, u32, pu32]
+        l.nori_devtest_tail_lookup.argtypes = [pu32, u32, pu32, u32, pu32, pu32]
+        l.nori_devtest_coop_scan.argtypes = [pf, u32, pf, pf, pf, pu8, u32, C.c_int, pu32]
+        l.nori_devtest_prim_forms.argtypes = []
+        l.nori_devtest_prim_hit.argtypes = [C.c_int, pf, pf, u32, pu32]
         _lib = l
     return _lib
 
@@ -118,3 +129,53 @@ def glass(integrator, center, radius, desc, seed, o, d, beta):
     s = GLASS_STATE
     return {"flags": out[:, 0], "input": out[:, 2:2 + s], "step": out[:, 2 + s:2 + 2 * s],
             "bounce": out[:, 2 + 2 * s:2 + 3 * s]}
+
+
+def _up(a):
+    return a.ctypes.data_as(C.POINTER(C.c_uint32))
+
+
+def tail_prefix(cnt):
+    """k_tail_prefix's body over the G counts: (G + 1,) uint32, pre[G] the total."""
+    cnt = np.ascontiguousarray(cnt, np.uint32).reshape(-1)
+    pre = np.full(cnt.size + 1, 0xDEADBEEF, np.uint32)
+    _check(lib().nori_devtest_tail_prefix(_up(cnt), cnt.size, _up(pre)), "nori_devtest_tail_prefix")
+    return pre
+
+
+def tail_lookup(pre, gids):
+    """(segment, queue index) of each gid through the prefix pre (G + 1 entries)."""
+    pre = np.ascontiguousarray(pre, np.uint32).reshape(-1)
+    gids = np.ascontiguousarray(gids, np.uint32).reshape(-1)
+    seg, slot = np.zeros(gids.size, np.uint32), np.zeros(gids.size, np.uint32)
+    _check(lib().nori_devtest_tail_lookup(_up(pre), pre.size - 1, _up(gids), gids.size, _up(seg), _up(slot)),
+           "nori_devtest_tail_lookup")
+    return seg, slot
+
+
+def coop_scan(records, root_min, root_max, rays, want, any_hit=False):
+    """coop_load + coop_scan<any_hit> in whole waves of 64 consecutive rays:
+    a dict of res (bool), t, u, v (float32) and prim (uint32) per ray."""
+    records, rays = _f32(records, 12), _f32(rays, 8)
+    want = np.ascontiguousarray(want, np.uint8).reshape(-1)
+    n = rays.shape[0]
+    _rows(n, want)
+    lo, hi = np.asarray(root_min, np.float32), np.asarray(root_max, np.float32)
+    out = np.zeros((n, 5), np.uint32)
+    _check(lib().nori_devtest_coop_scan(_fp(records), records.shape[0], _fp(lo), _fp(hi), _fp(rays),
+                                        want.ctypes.data_as(C.POINTER(C.c_uint8)), n, int(any_hit), _up(out)),
+           "nori_devtest_coop_scan")
+    return {"res": out[:, 0] != 0, "t": out[:, 1].copy().view(np.float32), "prim": out[:, 2].copy(),
+            "u": out[:, 3].copy().view(np.float32), "v": out[:, 4].copy().view(np.float32)}
+
+
+def prim_hit(form, records, rays):
+    """Ray i against record i with one of the forms above: hit (bool), t, u, v
+    (float32); BOX: record = (min, ., max, ., unused), returns ok, tnear, 0, 0."""
+    records, rays = _f32(records, 12), _f32(rays, 8)
+    n = rays.shape[0]
+    _rows(n, records)
+    out = np.zeros((n, 4), np.uint32)
+    _check(lib().nori_devtest_prim_hit(form, _fp(records), _fp(rays), n, _up(out)), "nori_devtest_prim_hit")
+    return (out[:, 0] != 0, out[:, 1].copy().view(np.float32), out[:, 2].copy().view(np.float32),
+            out[:, 3].copy().view(np.float32))

@@ -1,6 +1,9 @@
 """Unit tests of the device code of device_math.h and shading.h, run on the GPU
 through libnori_devtest.so (csrc/devtest.hip, tests/devtest_util.py) -- the
-routines the image-parity tests only see through whole renders.
+routines the image-parity tests only see through whole renders.  The library
+also covers the tail finisher's pieces (k_tail_prefix's body, the path
+lookup of tail_index.h, coop_scan) and the primitive tests of scan.h
+(tri_hit*, sphere_hit*, box_test): tests/test_gpu_finish_tail.py.
 
 a. the fast-math forms (sqrt_rn, rcp_rn, rcp_full and the FAST variants of
    fsqrt, normalize, frame_from, fresnel) against IEEE, bit for bit, and
