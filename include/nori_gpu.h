@@ -919,6 +919,67 @@ int nori_gpu_film_splat(nori_gpu_ctx *ctx, const nori_gpu_splat_desc *desc, cons
 int nori_gpu_film_splat_passes(nori_gpu_ctx *ctx, const nori_gpu_render_desc *desc, const float *pos,
                                const float *val, float *rgbw, nori_gpu_stats *stats);
 
+/* ---- film gather: the film splat's adjoint ----
+ * (no reference counterpart; deviation D19)
+ * nori_film_splat is linear in val; its adjoint is a gather: every sample reads
+ * the film cells of its own window with the weights it was splatted with.
+ * The statement, on the host.  pos: n x 2 floats; val: n x 3 floats or NULL;
+ * grad_rgbw: (H+2b) x (W+2b) x 4, read only -- channel 3 is never read, the
+ * weight channel of the splat does not depend on val; grad_val: n x 3 floats,
+ * WRITTEN, not added into.  For each sample i:
+ *  1. Steps 1 and 2 of nori_film_splat decide the owner and whether the sample
+ *     is kept: the position, the owner and, with val != NULL, Color3f::isValid
+ *     of val[i].  A dropped sample gets the row (0, 0, 0) and is counted in
+ *     counts[1] (it added nothing to the film, so its derivative is zero); a
+ *     kept one is counted in counts[0].
+ *  2. A kept sample uses the window and the weights of step 3 there (px, py,
+ *     the window clipped to the owner block's tile, wx, wy from the table).
+ *     For c = r, g, b: acc = 0.0f; for cy ascending, then cx ascending:
+ *     acc = acc + (G[c] * wx) * wy, G = cell (ox + cx, oy + cy) of grad_rgbw,
+ *     each a single float operation in the order written;
+ *     grad_val[3 i + c] = acc.  An empty window gives zeros.
+ * pos gets no derivative: the tabulated filter is piecewise constant in the
+ * position.  The device calls below produce the same float32 terms
+ * (G[c] * wx) * wy bit for bit and may differ only in the order of a sample's
+ * additions.  NORI_ERR_INVALID: a null argument (val may be NULL), an empty
+ * frame, ordered with n not a multiple of H W. */
+int nori_film_gather(const nori_scene_desc *scene, uint64_t n, int ordered, const float *pos,
+                     const float *val, const float *grad_rgbw, float *grad_val, uint64_t counts[2]);
+
+typedef struct nori_gpu_gather_desc {
+    uint64_t n;                   /* samples                                   */
+    int32_t on_device;            /* pos, val, grad_rgbw and grad_val are device
+                                     memory on the context's device            */
+    uint32_t reserved;            /* must be 0                                 */
+} nori_gpu_gather_desc;
+
+/* nori_film_gather on the context's device, for a context of any integrator and
+ * traversal mode.  Device arrays are used in place (pos, val and grad_val
+ * 4-byte, grad_rgbw 16-byte aligned, all checked to be device memory).  Of
+ * host arrays grad_rgbw is copied once into a context-owned buffer, pos and val
+ * are staged in chunks of at most NORI_QUERY_CHUNK samples (the passes layout:
+ * whole passes, at least one) and each chunk's rows are copied back.  val may
+ * be NULL.  stats (may be NULL): samples = kept, invalid_samples = zero rows,
+ * ms_total, ms_splat = HIP-event time of the kernels.  Blocking, on the
+ * context's stream.  A refusal launches nothing and leaves the context usable.
+ * nori_gpu_film_gather: samples anywhere on the image (ordered = 0).  n == 0 is
+ * a no-op.  NORI_ERR_INVALID: a null argument, reserved != 0, a device pointer
+ * that is misaligned or not device memory. */
+int nori_gpu_film_gather(nori_gpu_ctx *ctx, const nori_gpu_gather_desc *desc, const float *pos,
+                         const float *val, const float *grad_rgbw, float *grad_val,
+                         nori_gpu_stats *stats);
+/* nori_gpu_film_gather_passes: the layout of nori_gpu_camera_rays (ordered = 1)
+ * -- pos: pass_count x H x W x 2, val (or NULL) and grad_val: pass_count x H x
+ * W x 3.  From `desc`: pass_count (0 = the scene's sampleCount), num_blocks /
+ * block_ids (only the selected blocks' pixels are read and written, every other
+ * entry of grad_val is left untouched) and output_on_device (which covers all
+ * four arrays); the other fields are ignored.  NORI_ERR_INVALID: as
+ * nori_gpu_film_splat_passes.  Environment, read at every call:
+ * NORI_GATHER_PASSES -- the passes one work-group walks (default: at most 4). */
+int nori_gpu_film_gather_passes(nori_gpu_ctx *ctx, const nori_gpu_render_desc *desc, const float *pos,
+                                const float *val, const float *grad_rgbw, float *grad_val,
+                                nori_gpu_stats *stats);
+
 /* ---- dynamic geometry: new vertex positions, the BVH refitted on the device ----
  * (no reference counterpart: the reference builds its BVH once, in
  * Scene::activate; deviation D14) */

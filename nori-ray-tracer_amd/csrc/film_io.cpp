@@ -14,6 +14,8 @@
 //   (host statement of k_guided, denoise.hip).
 // nori_film_splat: caller-supplied samples filtered into the film (the host
 //   statement of k_splat_pos / k_splat_scatter, kernels_film.hip).
+// nori_film_gather: its adjoint (the host statement of k_gather_pos /
+//   k_gather_scatter, kernels_gather.hip).
 #include <zlib.h>
 
 #include <algorithm>
@@ -261,6 +263,50 @@ extern "C" int nori_film_splat(const nori_scene_desc *scene, uint64_t n, int ord
                     f[1] += (g * wx) * wy;
                     f[2] += (b * wx) * wy;
                     f[3] += (1.0f * wx) * wy;
+                }
+            }
+        }
+        return NORI_OK;
+    });
+}
+
+// The film splat's adjoint, stated at its declaration (nori_gpu.h); the device
+// versions are k_gather_pos and k_gather_scatter (kernels_gather.hip).
+extern "C" int nori_film_gather(const nori_scene_desc *scene, uint64_t n, int ordered, const float *pos, const float *val,
+                                const float *grad_rgbw, float *grad_val, uint64_t counts[2]) {
+    return nori::guarded([&] {
+        using namespace nori;
+        if (!scene || !pos || !grad_rgbw || !grad_val || !counts) return fail(NORI_ERR_INVALID, "null argument");
+        const int W = scene->camera.width, H = scene->camera.height;
+        if (W <= 0 || H <= 0) return fail(NORI_ERR_INVALID, "nori_film_gather: an empty frame");
+        const uint64_t WH = (uint64_t)W * (uint64_t)H;
+        if (ordered && n % WH != 0) return fail(NORI_ERR_INVALID, "nori_film_gather: ordered with n not a multiple of H * W");
+        FilmGeom F{};
+        F.W = W, F.H = H, F.B = film_border(scene->camera);
+        F.rad = scene->camera.filter_radius;
+        F.lk = NORI_FILTER_RESOLUTION / scene->camera.filter_radius;
+        filter_table(scene->camera, F.filter);
+        const int FW = W + 2 * F.B;
+        counts[0] = counts[1] = 0;
+        for (uint64_t i = 0; i < n; ++i) {
+            const uint64_t pix = i % WH;
+            float *out = grad_val + 3 * i;
+            out[0] = out[1] = out[2] = 0.0f;
+            PutWindow w;
+            if (!film_window(F, ordered != 0, (int)(pix % (uint64_t)W), (int)(pix / (uint64_t)W), pos[2 * i], pos[2 * i + 1], w) ||
+                (val && !film_color_valid(val[3 * i], val[3 * i + 1], val[3 * i + 2]))) {
+                ++counts[1];
+                continue;
+            }
+            ++counts[0];
+            for (int cy = w.y0; cy <= w.y1; ++cy) {
+                const float wy = film_weight(F.filter, F.lk, cy, w.py);
+                for (int cx = w.x0; cx <= w.x1; ++cx) {
+                    const float wx = film_weight(F.filter, F.lk, cx, w.px);
+                    const float *g = grad_rgbw + 4 * ((size_t)(w.oy + cy) * FW + (w.ox + cx));
+                    out[0] = out[0] + (g[0] * wx) * wy;
+                    out[1] = out[1] + (g[1] * wx) * wy;
+                    out[2] = out[2] + (g[2] * wx) * wy;
                 }
             }
         }

@@ -224,6 +224,15 @@ hipError_t launch_splat_pos(const FilmGeom &F, const int4 *blocks, uint32_t nblo
 constexpr bool kScatterRows = NORI_SCATTER_ROWS != 0;
 hipError_t launch_splat_scatter(const FilmGeom &F, uint64_t n, bool rows, const float *pos, const float *val,
                                 float *film, float *var, unsigned long long *dropped, hipStream_t st);
+// The splat's adjoint (kernels_gather.hip; stated at nori_film_gather in
+// nori_gpu.h).  All pointers are device memory; val may be null; grad: (H+2B) x
+// (W+2B) x 4, 16-byte aligned, read only; gval: three floats per sample,
+// written; *dropped += the zero rows.  The layouts are the splat launches'.
+hipError_t launch_gather_pos(const FilmGeom &F, const int4 *blocks, uint32_t nblocks, uint32_t passes,
+                             uint32_t passes_per_wg, uint64_t stride, const float *pos, const float *val,
+                             const float *grad, float *gval, unsigned long long *dropped, hipStream_t st);
+hipError_t launch_gather_scatter(const FilmGeom &F, uint64_t n, const float *pos, const float *val, const float *grad,
+                                 float *gval, unsigned long long *dropped, hipStream_t st);
 // The adaptive sampler's block error (block_error.hip; the metric is stated
 // at nori_film_block_error in nori_gpu.h): stats W x H x 8 on the device
 // (16-byte aligned), ids = the nblocks frame blocks to evaluate (null: blocks

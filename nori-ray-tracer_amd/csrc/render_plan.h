@@ -43,6 +43,10 @@ PartSplit part_split(uint32_t G, uint32_t parts);
 uint32_t splat_passes(uint32_t np, size_t nblocks, uint32_t target_wgs, const char *text);
 // ... and of k_splat_pos (film_splat.hip); text: NORI_SPLAT_POS_PASSES.
 uint32_t passes_per_wg(uint32_t np, size_t nblocks, const char *text);
+// ... and walked by one work-group of k_gather_pos: passes_per_wg's, at most 4
+// unless the text names a range (1 .. np, at most 65535 ranges a launch);
+// text: NORI_GATHER_PASSES.
+uint32_t gather_passes(uint32_t np, size_t nblocks, const char *text);
 // Passes per launch of the calls that run one kernel over M pixels: about 16M elements.
 uint32_t pass_chunk(uint32_t passes, uint32_t M);
 // NORI_QUERY_CHUNK: the most elements of a host array staged at once.

@@ -27,7 +27,7 @@ from ._abi import NoriError, check, lib  # noqa: F401
 __all__ = ["load_scene", "Scene", "GpuRenderer", "RenderThread", "NoriError", "device_count",
            "develop", "write_exr", "write_png", "read_exr", "film_variance", "ldr_bytes", "variance_gray",
            "denoise", "read_image", "block_error", "film_features", "denoise_guided", "film_denoise_guided",
-           "scene_surface", "bvh_refit", "bvh_rebuild", "film_splat"]
+           "scene_surface", "bvh_refit", "bvh_rebuild", "film_splat", "film_gather"]
 
 
 def _fptr(a):
@@ -184,6 +184,29 @@ def film_splat(scene, pos, val, ordered=False, out=None, variance=None):
     check(lib().nori_film_splat(scene.desc_ptr, pos.shape[0], int(bool(ordered)), C.c_void_p(pos.ctypes.data),
                                 C.c_void_p(val.ctypes.data), C.c_void_p(out.ctypes.data),
                                 None if variance is None else C.c_void_p(variance.ctypes.data), counts))
+    return out, (int(counts[0]), int(counts[1]))
+
+
+def film_gather(scene, pos, grad, val=None, ordered=False):
+    """The film splat's adjoint on the host (nori_film_gather, where the operation is stated):
+    with `grad` (H+2b, W+2b, 4) the derivative of some scalar by the film that film_splat(scene,
+    pos, val, ordered) returns, the derivative by `val` -- every sample reads the cells of its own
+    window with the weights it was splatted with.  Returns (grad_val (n, 3), (kept, dropped)); a
+    sample film_splat drops gets a zero row (val=None: no value check).  pos has no derivative.
+    GpuRenderer.film_gather and film_gather_passes are the device versions."""
+    pos = np.ascontiguousarray(pos, dtype=np.float32).reshape(-1, 2)
+    grad = np.ascontiguousarray(grad, dtype=np.float32)
+    if grad.shape != scene.film_shape():
+        raise ValueError(f"film_gather: grad shape {grad.shape} != {scene.film_shape()}")
+    if val is not None:
+        val = np.ascontiguousarray(val, dtype=np.float32).reshape(-1, 3)
+        if pos.shape[0] != val.shape[0]:
+            raise ValueError(f"film_gather: {pos.shape[0]} positions and {val.shape[0]} values")
+    out = np.zeros((pos.shape[0], 3), np.float32)
+    counts = (C.c_uint64 * 2)()
+    check(lib().nori_film_gather(scene.desc_ptr, pos.shape[0], int(bool(ordered)), C.c_void_p(pos.ctypes.data),
+                                 None if val is None else C.c_void_p(val.ctypes.data), C.c_void_p(grad.ctypes.data),
+                                 C.c_void_p(out.ctypes.data), counts))
     return out, (int(counts[0]), int(counts[1]))
 
 
@@ -860,6 +883,66 @@ class GpuRenderer:
         rd.output_on_device = dev
         rd.variance_out = var
         self._call(lib().nori_gpu_film_splat_passes, C.byref(rd), C.c_void_p(p), C.c_void_p(v), C.c_void_p(film))
+        return ret
+
+    def _gather_args(self, name, pos, grad, val, n, out):
+        """(on_device, n, pos, val, grad, out addresses, the rows to return, keep-alive) of a film
+        gather: all numpy (host form) or all device addresses / torch tensors with a device out=."""
+        given = [a for a in (pos, grad, val) if a is not None]
+        host = [isinstance(a, np.ndarray) for a in given]
+        if any(host) != all(host):
+            raise ValueError(f"{name}: pos, grad and val must all be numpy arrays or all be device addresses")
+        if not all(host):
+            if out is None or isinstance(out, np.ndarray):
+                raise ValueError(f"{name}: device arrays need a device out=")
+            if n is None:
+                if not hasattr(pos, "numel"):
+                    raise ValueError(f"{name}: int device addresses need the sample count")
+                n = pos.numel() // 2
+            return 1, int(n), _addr(pos), _addr(val), _addr(grad), _addr(out), None, ()
+        pos = np.ascontiguousarray(pos, dtype=np.float32).reshape(-1, 2)
+        grad = np.ascontiguousarray(grad, dtype=np.float32)
+        if grad.shape != self.scene.film_shape():
+            raise ValueError(f"{name}: grad shape {grad.shape} != {self.scene.film_shape()}")
+        if val is not None:
+            val = np.ascontiguousarray(val, dtype=np.float32).reshape(-1, 3)
+            if pos.shape[0] != val.shape[0]:
+                raise ValueError(f"{name}: {pos.shape[0]} positions and {val.shape[0]} values")
+        if n is not None and int(n) != pos.shape[0]:
+            raise ValueError(f"{name}: {pos.shape[0]} samples, expected {int(n)}")
+        if out is None:
+            out = np.zeros((pos.shape[0], 3), np.float32)
+        assert (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.flags.c_contiguous
+                and out.size == 3 * pos.shape[0])
+        return (0, pos.shape[0], pos.ctypes.data, None if val is None else val.ctypes.data, grad.ctypes.data,
+                out.ctypes.data, out, (pos, val, grad))
+
+    def film_gather(self, pos, grad, val=None, n=None, out=None):
+        """The adjoint of film_splat (nori_gpu_film_gather; stated at nori_film_gather in nori_gpu.h):
+        with `grad` (H+2b, W+2b, 4) the derivative by the film, the derivative by val -- (n, 3), a
+        zero row for a sample film_splat drops (val=None: no value check).  With numpy arrays the
+        rows are returned (written into `out` when given).  With torch tensors or int device
+        addresses (then with n=), `out` must be a device array of n x 3 floats (grad 16-byte
+        aligned), everything is used in place and None is returned; the buffers must be ready
+        before the call.  last_stats: samples = kept, invalid_samples = zero rows, ms_splat."""
+        dev, n, p, v, g, o, ret, keep = self._gather_args("film_gather", pos, grad, val, n, out)
+        gd = _abi.GatherDesc(n, dev, 0)
+        self._call(lib().nori_gpu_film_gather, C.byref(gd), C.c_void_p(p), C.c_void_p(v), C.c_void_p(g), C.c_void_p(o))
+        return ret
+
+    def film_gather_passes(self, pos, grad, val=None, passes=None, blocks=None, out=None):
+        """The adjoint of film_splat_passes (nori_gpu_film_gather_passes): pos (passes, H, W, 2), val
+        (passes, H, W, 3) or None; returns (passes, H, W, 3).  Only the rows of the pixels of
+        `blocks` (all if None) are written: every other entry of `out` stays as it is (zero in a
+        new array).  Host and device forms, `out` and last_stats as film_gather."""
+        rd, ids = self._desc(passes, 0, blocks, 0, 0, False)
+        n = rd.pass_count * self.scene.width * self.scene.height if rd.pass_count else None
+        dev, n, p, v, g, o, ret, keep = self._gather_args("film_gather_passes", pos, grad, val, n, out)
+        rd.output_on_device = dev
+        self._call(lib().nori_gpu_film_gather_passes, C.byref(rd), C.c_void_p(p), C.c_void_p(v), C.c_void_p(g),
+                   C.c_void_p(o))
+        if ret is not None and out is None:
+            ret = ret.reshape(-1, self.scene.height, self.scene.width, 3)
         return ret
 
     def _vertex_arg(self, a, what):

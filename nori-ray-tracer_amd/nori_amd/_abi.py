@@ -148,6 +148,11 @@ class SplatDesc(C.Structure):
     _fields_ = [("n", C.c_uint64), ("on_device", C.c_int32), ("reserved", C.c_uint32), ("variance_out", C.c_void_p)]
 
 
+class GatherDesc(C.Structure):
+    """nori_gpu_gather_desc: the descriptor of nori_gpu_film_gather."""
+    _fields_ = [("n", C.c_uint64), ("on_device", C.c_int32), ("reserved", C.c_uint32)]
+
+
 class LiDesc(C.Structure):
     """nori_gpu_li_desc: the descriptor of nori_gpu_li."""
     _fields_ = [("n", C.c_uint32), ("on_device", C.c_int32), ("seed", C.c_uint64), ("stream_base", C.c_uint64),
@@ -244,6 +249,12 @@ SIGNATURES = {
                                       C.POINTER(Stats)]),
     "nori_gpu_film_splat_passes": (C.c_int, [C.c_void_p, C.POINTER(RenderDesc), C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.POINTER(Stats)]),
+    "nori_film_gather": (C.c_int, [C.POINTER(SceneDesc), C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.POINTER(C.c_uint64)]),
+    "nori_gpu_film_gather": (C.c_int, [C.c_void_p, C.POINTER(GatherDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.POINTER(Stats)]),
+    "nori_gpu_film_gather_passes": (C.c_int, [C.c_void_p, C.POINTER(RenderDesc), C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.POINTER(Stats)]),
     "nori_gpu_update_vertices": (C.c_int, [C.c_void_p, C.POINTER(UpdateDesc), C.POINTER(UpdateStats)]),
     "nori_gpu_bvh_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint32)]),
     "nori_scene_bvh_refit": (C.c_int, [C.POINTER(SceneDesc), C.POINTER(C.c_float), C.POINTER(C.c_float),
@@ -273,7 +284,8 @@ ADDED_IN_7 = {"nori_gpu_query", "nori_scene_surface", "nori_gpu_camera_rays", "n
               "nori_gpu_bvh_read", "nori_scene_bvh_refit", "nori_scene_bvh_rebuild", "nori_gpu_rebuild_bvh",
               "nori_scene_shade_rtc", "nori_gpu_shade_rtc_info", "nori_gpu_bsdf_eval", "nori_gpu_bsdf_sample",
               "nori_gpu_emitter_sample", "nori_gpu_emitter_eval", "nori_gpu_sample_uniforms", "nori_film_splat",
-              "nori_gpu_film_splat", "nori_gpu_film_splat_passes", "nori_scene_scan_fast", "nori_gpu_li"}
+              "nori_gpu_film_splat", "nori_gpu_film_splat_passes", "nori_scene_scan_fast", "nori_gpu_li",
+              "nori_film_gather", "nori_gpu_film_gather", "nori_gpu_film_gather_passes"}
 
 COMM_ID_BYTES = 128
 SHARD_PASSES, SHARD_BLOCKS = 0, 1

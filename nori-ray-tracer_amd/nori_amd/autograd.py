@@ -1,0 +1,112 @@
+"""The film as a differentiable torch operation.
+
+    from nori_amd import autograd
+    film = autograd.film_splat_passes(r, pos, val)      # val.requires_grad: the film carries a graph
+    img = autograd.develop(r.scene, film)                # ImageBlock::toBitmap in torch
+    ((img - target) ** 2).sum().backward()               # val.grad through the scene's own filter
+
+The forward is GpuRenderer.film_splat / film_splat_passes into a new film; the splat is linear in
+`val`, and the backward is its adjoint, GpuRenderer.film_gather / film_gather_passes: every sample
+reads the incoming gradient over the window it was splatted into, with the same weights
+(nori_film_gather in nori_gpu.h).  `pos` never receives a gradient: the tabulated filter is
+piecewise constant in the position.  The library runs on its own stream and its calls block, so
+each call is preceded by a synchronisation of torch's current stream on the context's device.
+
+This module alone imports torch; `import nori_amd` works without it."""
+import torch
+from torch.autograd.function import once_differentiable
+
+__all__ = ["film_splat", "film_splat_passes", "develop"]
+
+
+def _device(r):
+    return torch.device("cuda", r.device)
+
+
+def _input(r, a):
+    """`a` as a contiguous float32 tensor on the context's device (a tracked conversion)."""
+    return torch.as_tensor(a).to(device=_device(r), dtype=torch.float32).contiguous()
+
+
+def _ready(r):
+    torch.cuda.current_stream(_device(r)).synchronize()
+
+
+class _FilmSplat(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, r, pos, val):
+        film = torch.zeros(r.scene.film_shape(), dtype=torch.float32, device=_device(r))
+        _ready(r)
+        r.film_splat(pos, val, n=val.numel() // 3, out=film)
+        ctx.r = r
+        ctx.save_for_backward(pos, val)
+        return film
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad):
+        pos, val = ctx.saved_tensors
+        grad = grad.contiguous()
+        grad_val = torch.zeros_like(val)
+        _ready(ctx.r)
+        ctx.r.film_gather(pos, grad, val, n=val.numel() // 3, out=grad_val)
+        return None, None, grad_val
+
+
+class _FilmSplatPasses(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, r, pos, val, passes, blocks):
+        film = torch.zeros(r.scene.film_shape(), dtype=torch.float32, device=_device(r))
+        _ready(r)
+        r.film_splat_passes(pos, val, passes=passes, blocks=blocks, out=film)
+        ctx.r, ctx.passes, ctx.blocks = r, passes, blocks
+        ctx.save_for_backward(pos, val)
+        return film
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad):
+        pos, val = ctx.saved_tensors
+        grad = grad.contiguous()
+        grad_val = torch.zeros_like(val)  # zero: the rows of unselected blocks are not written
+        _ready(ctx.r)
+        ctx.r.film_gather_passes(pos, grad, val, passes=ctx.passes, blocks=ctx.blocks, out=grad_val)
+        return None, None, grad_val, None, None
+
+
+def film_splat(r, pos, val):
+    """GpuRenderer.film_splat(pos, val) into a new film tensor (H+2b, W+2b, 4), differentiable in
+    val: pos (n, 2), val (n, 3)."""
+    return _FilmSplat.apply(r, _input(r, pos).detach(), _input(r, val))
+
+
+def film_splat_passes(r, pos, val, passes=None, blocks=None):
+    """GpuRenderer.film_splat_passes(pos, val, passes, blocks) into a new film tensor,
+    differentiable in val: pos (passes, H, W, 2), val (passes, H, W, 3); passes=None is the
+    scene's sampleCount.  The samples of unselected blocks get a zero gradient."""
+    pos, val = _input(r, pos).detach(), _input(r, val)
+    W, H = r.scene.width, r.scene.height
+    if passes is None:
+        passes = int(r.scene.spp)
+    if val.numel() != 3 * passes * H * W or pos.numel() != 2 * passes * H * W:
+        raise ValueError(f"film_splat_passes: pos {tuple(pos.shape)} and val {tuple(val.shape)}, expected "
+                         f"{(passes, H, W, 2)} and {(passes, H, W, 3)}")
+    return _FilmSplatPasses.apply(r, pos, val, passes, None if blocks is None else [int(b) for b in blocks])
+
+
+def develop(scene, film):
+    """ImageBlock::toBitmap (nori_amd.develop) in differentiable torch operations: the border
+    cropped, rgb / w where w != 0, else 0 -- (H, W, 3).  The denominator of a w == 0 cell is
+    replaced by 1 before the division, so no NaN gradient appears; the quotient of the two floats
+    is taken in float64 and rounded to float32, which is the correctly rounded float32 quotient
+    (53 >= 2 * 24 + 2 bits): the values equal nori_amd.develop's bit for bit, whatever torch's
+    float32 division does."""
+    if tuple(film.shape) != tuple(scene.film_shape()):
+        raise ValueError(f"film shape {tuple(film.shape)} != {scene.film_shape()}")
+    b, H, W = scene.border, scene.height, scene.width
+    crop = film[b:H + b, b:W + b]
+    rgb, w = crop[..., 0:3], crop[..., 3:4]
+    nz = w != 0
+    safe = torch.where(nz, w, torch.ones_like(w))
+    q = (rgb.double() / safe.double()).float()
+    return torch.where(nz, q, torch.zeros_like(q))
