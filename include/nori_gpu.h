@@ -54,6 +54,9 @@
  *                         (dynamic geometry: a linear BVH built on the device
  *                          for the positions as they are now; no reference
  *                          counterpart)
+ *   nori_scene_surface_grad, nori_gpu_surface_grad
+ *                         (the hit record's adjoint in the vertex positions and
+ *                          normals; no reference counterpart)
  *   nori_scene_scan_rtc, nori_scene_shade_rtc, nori_gpu_shade_rtc_info
  *                         (the scene-specialised kernels compiled at context
  *                          creation through hipRTC; no reference counterpart)
@@ -605,6 +608,70 @@ typedef struct nori_gpu_query_desc {
 int nori_scene_surface(const nori_scene_desc *scene, uint32_t n, const float *rays,
                        const nori_gpu_hit *hits, nori_gpu_surface *out);
 
+/* The record's adjoint in the mesh vertices, on the host (no device needed):
+ * for a gradient grad_surf[i] of some scalar in record i (the record's own
+ * layout, so an (n, 16) float gradient of a record array passes through
+ * unchanged), what that scalar's gradient in the vertex positions and vertex
+ * normals receives from hit i.  This is the one statement; the device call
+ * (nori_gpu_surface_grad) forms the same terms and adds them in any order.
+ *   positions, normals: num_vertices x 3 floats each, the geometry the record
+ *     is differentiated at; NULL: the scene's own arrays.
+ *   Of grad_surf[i] only p, t, ng and ns are read (g_p, g_t, g_ng, g_ns); the
+ *     words at prim, shape, uv and bary are ignored and may hold anything (NaN
+ *     bit patterns included): uv and bary have no gradient, texture
+ *     coordinates are not vertices that nori_gpu_update_vertices moves.
+ *   What is held fixed: the hit set (prim), the barycentrics (u, v) for p and
+ *     ns, the ray (o, d) for t.  So g_p is the derivative of the material
+ *     point at fixed barycentrics; a caller who wants the point where the
+ *     fixed ray meets the moving triangle (p = o + t d) adds d . g_p to g_t
+ *     and passes g_p = 0.  t is differentiated as the exact function
+ *     t = N.(p0 - o) / (N.d) whose fp32 value the tracer returns.
+ * Hit i: prim, u, v, t from hits[i]; o = rays[8i .. 8i+2], d = rays[8i+4 ..
+ * 8i+6]; vertices p0, p1, p2 and vertex normals n0, n1, n2 of triangle prim
+ * (vertex ids f0, f1, f2).  Every operation is fp32, unfused, in this order
+ * (dot(a, b) = (a.x b.x + a.y b.y) + a.z b.z; cross as usual, each component
+ * one subtraction of two products; vectors componentwise):
+ *     b   = 1 - (u + v)
+ *     e1  = p1 - p0;  e2 = p2 - p0;  N = cross(e1, e2)
+ *     len = sqrt(dot(N, N));  D = dot(N, d)
+ *     len > 0 and D != 0, else the hit contributes nothing
+ *     ng  = N / len
+ *     g'  = g_ng on a mesh with vertex normals, g_ng + g_ns on one without (ns = ng there)
+ *     gN  = (g' - ng * dot(ng, g')) / len
+ *     s   = g_t / D;  ph = o + d * t
+ *     gN  = gN + (p0 - ph) * s
+ *     ge1 = cross(e2, gN);  ge2 = cross(gN, e1)
+ *     g_p0 = (g_p * b + N * s) - (ge1 + ge2)
+ *     g_p1 = g_p * u + ge1
+ *     g_p2 = g_p * v + ge2
+ *   and, on a mesh with vertex normals and no normal map,
+ *     M   = (n0 * b + n1 * u) + n2 * v;  lm = sqrt(dot(M, M))
+ *     lm > 0, else g_n0 = g_n1 = g_n2 = 0 (the position terms stay)
+ *     ns  = M / lm
+ *     gM  = (g_ns - ns * dot(ns, g_ns)) / lm
+ *     g_n0 = gM * b;  g_n1 = gM * u;  g_n2 = gM * v
+ *   On a normal-mapped shape g_ns contributes nothing, to positions or normals:
+ *   the frame built around the interpolated normal is piecewise (Frame(n)
+ *   branches on the normal's components) and the mapped normal is not
+ *   renormalised, so that derivative is left out; g_p, g_t and g_ng still count.
+ *   A miss (prim < 0) and a sphere hit contribute nothing.
+ * terms (NULL, or n x 18 floats): g_p0, g_p1, g_p2, g_n0, g_n1, g_n2 of hit i
+ * at terms[18 i], zeros where the hit contributes nothing or the mesh has no
+ * normal terms.
+ * The sums: grad_positions[3 f0 ..] receives g_p0, [3 f1 ..] g_p1, [3 f2 ..]
+ * g_p2 (grad_normals likewise; NULL: the normal terms are not formed and the
+ * positions' result is the same bits).  Each destination float is accumulated
+ * in float64 over the hits in order and the sum is added once, in float64, to
+ * the value already there and rounded to fp32; a destination that receives no
+ * term is not touched.
+ * NORI_ERR_INVALID, nothing written: a null scene, rays, hits, grad_surf or
+ * grad_positions; a primitive id outside the scene; a non-finite position or
+ * normal (of the arrays in use). */
+int nori_scene_surface_grad(const nori_scene_desc *scene, const float *positions, const float *normals,
+                            uint32_t n, const float *rays, const nori_gpu_hit *hits,
+                            const nori_gpu_surface *grad_surf, float *grad_positions, float *grad_normals,
+                            float *terms);
+
 /* Trace desc->n rays as nori_gpu_trace does (the same kernels: `hits` is
  * bit-identical to its result) and, with `surf`, fill the record of every
  * closest hit (nori_scene_surface).  hits and surf may each be NULL, not both.
@@ -623,6 +690,37 @@ int nori_scene_surface(const nori_scene_desc *scene, uint32_t n, const float *ra
  * (wall time), ms_extend / ms_shade = HIP-event time of the trace / record kernels. */
 int nori_gpu_query(nori_gpu_ctx *ctx, const nori_gpu_query_desc *desc, const float *rays,
                    nori_gpu_hit *hits, nori_gpu_surface *surf, nori_gpu_stats *stats);
+
+/* nori_scene_surface_grad on the device, for the vertices the context holds
+ * now (as nori_gpu_create loaded them or nori_gpu_update_vertices last set
+ * them; the tree plays no part, so nori_gpu_rebuild_bvh changes nothing).  The
+ * kernel forms the statement's fp32 terms bit for bit and ADDS them into
+ * grad_positions and, unless NULL, grad_normals (num_vertices x 3 floats each)
+ * with float atomics, after summing on chip the terms of a work-group's hits
+ * on the same triangle: the order of the additions is not fixed, so a sum of
+ * several terms agrees with the statement's to fp32 rounding of its partial
+ * sums, not bit for bit (a destination with one term does).
+ * on_device: rays, hits, grad_surf (16-byte aligned) and the two outputs
+ * (4-byte aligned) are device memory on the context's device, used in place;
+ * nothing is allocated per call.  Otherwise they are host arrays: the inputs
+ * pass through the context's staging buffers in chunks of at most
+ * NORI_QUERY_CHUNK hits, the sums are formed in zeroed device buffers and added
+ * to the caller's arrays once at the end.  Works on a context of any
+ * integrator and either traversal mode.  Blocking, on the context's stream.
+ * A primitive id outside the scene contributes nothing (the kernel cannot
+ * refuse).  n == 0 is a no-op.
+ * NORI_ERR_INVALID, nothing launched and nothing written: a null ctx, desc,
+ * rays, hits, grad_surf or grad_positions; reserved != 0; on_device with a
+ * misaligned pointer or one that is not device memory.
+ * stats (may be NULL): ms_total (wall time), ms_shade = HIP-event time of the kernel. */
+typedef struct nori_gpu_surface_grad_desc {
+    uint32_t n;            /* hits */
+    int32_t  on_device;    /* all five arrays are device pointers on the context's device */
+    uint32_t reserved[2];  /* must be 0 */
+} nori_gpu_surface_grad_desc;
+int nori_gpu_surface_grad(nori_gpu_ctx *ctx, const nori_gpu_surface_grad_desc *desc, const float *rays,
+                          const nori_gpu_hit *hits, const nori_gpu_surface *grad_surf,
+                          float *grad_positions, float *grad_normals, nori_gpu_stats *stats);
 
 /* Camera::sampleRay for the renderer's own samples: the primary ray of sample
  * (pass pass_begin + k, pixel pix = y W + x) at rays[8 (k H W + pix)] (o.xyz,

@@ -162,6 +162,15 @@ hipError_t launch_features(const DevScene &S, const uint32_t *pixels, uint32_t M
 // float4), i < n; all three arrays 16-byte aligned.
 hipError_t launch_surface(const DevScene &S, const float4 *rays, const float4 *hits, uint32_t n, float4 *out,
                           hipStream_t st);
+// The record's adjoint (kernels_surface_grad.hip k_surface_grad; stated at
+// nori_scene_surface_grad in nori_gpu.h): the terms of hit i < n, formed from
+// the scene's current pos / nrm, are added with float atomics into
+// grad_positions and (unless null) grad_normals, num_vertices x 3 floats each.
+// rays, hits and grad_surf (four float4 per hit) are 16-byte aligned; all
+// device memory.  A vertex id not below num_vertices adds nothing.
+hipError_t launch_surface_grad(const DevScene &S, uint32_t num_vertices, const float4 *rays, const float4 *hits,
+                               const float4 *grad_surf, uint32_t n, float *grad_positions, float *grad_normals,
+                               hipStream_t st);
 // Primary rays (kernels_query.hip k_camera_rays): the ray of sample (pass
 // pass_begin + k, pixel pix) for k in [k0, k0 + np) and the M entries of
 // `pixels` (y*W + x), written at rays[8 * (k * W * H + pix)]; np * M < 2^31.

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "ctx.h"
+#include "surface_grad.h"
 
 namespace nori {
 namespace {
@@ -232,6 +233,70 @@ int sample_uniforms(nori_gpu_ctx &c, const nori_gpu_render_desc &rd, uint32_t fi
     return NORI_OK;
 }
 
+// nori_gpu_surface_grad: k_surface_grad over the caller's hits, for the
+// vertices in c.pos / c.nrm as they are now.  Device arrays are checked and
+// used in place; host inputs pass through q_rays / q_hits / q_surf in chunks
+// of at most NORI_QUERY_CHUNK hits, and the sums are formed in sh_out / sh_in[0],
+// zeroed first, and added to the caller's arrays at the end.
+int surface_grad(nori_gpu_ctx &c, const nori_gpu_surface_grad_desc &gd, const float *rays, const nori_gpu_hit *hits,
+                 const nori_gpu_surface *grad_surf, float *grad_positions, float *grad_normals, nori_gpu_stats *stats) {
+    const auto t0 = std::chrono::steady_clock::now();
+    const char *name = "nori_gpu_surface_grad";
+    HIP_TRY(hipSetDevice(c.device));
+    const uint32_t n = gd.n, V = c.num_vertices;
+    if (gd.on_device) {
+        const void *all[5] = {rays, hits, grad_surf, grad_positions, grad_normals};
+        for (const void *p : all)
+            if (p) require_device_ptr(p, std::string(name) + ": on_device with a pointer that is not device memory");
+    }
+    // a scene without vertex normals has no normal terms: the instantiation without them runs
+    bool any_normals = false;
+    for (const DevShape &sh : c.hshapes) any_normals |= sh.type != NORI_SHAPE_SPHERE && sh.has_normals;
+    c.clock.reset(stats != nullptr);
+    auto run = [&](const void *r, const void *h, const void *g, uint32_t m, float *gp, float *gn) {
+        c.clock.span(c.stream, kKindShade, [&] {
+            return launch_surface_grad(c.S, V, (const float4 *)r, (const float4 *)h, (const float4 *)g, m, gp,
+                                       any_normals ? gn : nullptr, c.stream);
+        });
+    };
+    if (gd.on_device) {
+        run(rays, hits, grad_surf, n, grad_positions, grad_normals);
+        HIP_TRY(hipStreamSynchronize(c.stream));
+        c.clock.collect();
+    } else {
+        const size_t nfl = 3 * (size_t)V;
+        const bool gn = grad_normals && any_normals;
+        c.sh_out.ensure(4 * nfl);
+        HIP_TRY(hipMemsetAsync(c.sh_out.p, 0, 4 * nfl, c.stream));
+        if (gn) {
+            c.sh_in[0].ensure(4 * nfl);
+            HIP_TRY(hipMemsetAsync(c.sh_in[0].p, 0, 4 * nfl, c.stream));
+        }
+        const uint32_t chunk = std::min(n, query_chunk(std::getenv("NORI_QUERY_CHUNK")));
+        c.q_rays.ensure(32 * (size_t)chunk);
+        c.q_hits.ensure(16 * (size_t)chunk);
+        c.q_surf.ensure(64 * (size_t)chunk);
+        for (uint64_t i0 = 0; i0 < n; i0 += chunk) {
+            const uint32_t m = (uint32_t)std::min<uint64_t>(chunk, n - i0);
+            HIP_TRY(hipMemcpyAsync(c.q_rays.p, rays + 8 * i0, 32 * (size_t)m, hipMemcpyHostToDevice, c.stream));
+            HIP_TRY(hipMemcpyAsync(c.q_hits.p, hits + i0, 16 * (size_t)m, hipMemcpyHostToDevice, c.stream));
+            HIP_TRY(hipMemcpyAsync(c.q_surf.p, grad_surf + i0, 64 * (size_t)m, hipMemcpyHostToDevice, c.stream));
+            run(c.q_rays.p, c.q_hits.p, c.q_surf.p, m, c.sh_out.as<float>(), gn ? c.sh_in[0].as<float>() : nullptr);
+            HIP_TRY(hipStreamSynchronize(c.stream));
+            c.clock.collect();
+        }
+        std::vector<float> h(nfl);
+        HIP_TRY(hipMemcpy(h.data(), c.sh_out.p, 4 * nfl, hipMemcpyDeviceToHost));
+        for (size_t k = 0; k < nfl; ++k) grad_positions[k] += h[k];
+        if (gn) {
+            HIP_TRY(hipMemcpy(h.data(), c.sh_in[0].p, 4 * nfl, hipMemcpyDeviceToHost));
+            for (size_t k = 0; k < nfl; ++k) grad_normals[k] += h[k];
+        }
+    }
+    if (begin_stats(c, t0, stats)) stats->ms_shade = c.clock.ms[kKindShade];  // k_surface_grad
+    return NORI_OK;
+}
+
 }  // namespace
 }  // namespace nori
 
@@ -449,6 +514,92 @@ int nori_scene_surface(const nori_scene_desc *d, uint32_t n, const float *rays, 
             r.bary[0] = u, r.bary[1] = v;
         }
         return NORI_OK;
+    });
+}
+
+// The record's adjoint, its statement (nori_gpu.h): the terms are
+// surface_grad.h's, which k_surface_grad compiles too; the sums are float64
+// per destination, in hit order.  Everything is formed before anything is
+// written, so a refusal leaves the caller's arrays alone.
+int nori_scene_surface_grad(const nori_scene_desc *d, const float *positions, const float *normals, uint32_t n,
+                            const float *rays, const nori_gpu_hit *hits, const nori_gpu_surface *grad_surf,
+                            float *grad_positions, float *grad_normals, float *terms) {
+    return guarded([&] {
+        if (!d || !rays || !hits || !grad_surf || !grad_positions) return fail(NORI_ERR_INVALID, "null argument");
+        const float *P = positions ? positions : d->positions, *Nv = normals ? normals : d->normals;
+        const size_t nfl = 3 * (size_t)d->num_vertices;
+        for (const float *a : {P, Nv})
+            if (a)
+                for (size_t k = 0; k < nfl; ++k)
+                    if (!std::isfinite(a[k])) return fail(NORI_ERR_INVALID, "nori_scene_surface_grad: a non-finite position or normal");
+        std::vector<uint32_t> first(d->num_shapes + 1, 0u);  // first global primitive id of each shape
+        for (uint32_t s = 0; s < d->num_shapes; ++s)
+            first[s + 1] = first[s] + (d->shapes[s].type == NORI_SHAPE_SPHERE ? 1u : d->shapes[s].tri_count);
+        auto at3 = [](const float *a, size_t i) { return V3{a[3 * i], a[3 * i + 1], a[3 * i + 2]}; };
+        std::vector<float> tm(18 * (size_t)n, 0.0f);
+        std::vector<double> accp(nfl, 0.0), accn(grad_normals ? nfl : 0, 0.0);
+        std::vector<uint8_t> hasp(nfl, 0), hasn(grad_normals ? nfl : 0, 0);
+        for (uint32_t i = 0; i < n; ++i) {
+            const nori_gpu_hit &h = hits[i];
+            if (h.prim < 0) continue;
+            if ((uint32_t)h.prim >= first[d->num_shapes]) return fail(NORI_ERR_INVALID, "primitive id outside the scene");
+            const uint32_t s = (uint32_t)(std::upper_bound(first.begin(), first.end(), (uint32_t)h.prim) - first.begin()) - 1;
+            const nori_shape_desc &sd = d->shapes[s];
+            if (sd.type == NORI_SHAPE_SPHERE) continue;
+            const uint64_t tri = (uint64_t)sd.tri_offset + ((uint32_t)h.prim - first[s]);
+            if (tri >= d->num_triangles || !d->indices || !P) return fail(NORI_ERR_INVALID, "mesh range outside the scene arrays");
+            const uint32_t *f = d->indices + 3 * tri;
+            if (f[0] >= d->num_vertices || f[1] >= d->num_vertices || f[2] >= d->num_vertices)
+                return fail(NORI_ERR_INVALID, "vertex index out of range");
+            if (sd.has_normals && !Nv) return fail(NORI_ERR_INVALID, "a mesh with normals in a scene without a normal array");
+            const float *ray = rays + 8 * (size_t)i;
+            const nori_gpu_surface &g = grad_surf[i];
+            const V3 g_ng{g.ng[0], g.ng[1], g.ng[2]}, g_ns{g.ns[0], g.ns[1], g.ns[2]};
+            V3 tp[3], tn[3];
+            if (!surface_grad_positions(at3(P, f[0]), at3(P, f[1]), at3(P, f[2]), V3{ray[0], ray[1], ray[2]},
+                                        V3{ray[4], ray[5], ray[6]}, h.t, h.u, h.v, V3{g.p[0], g.p[1], g.p[2]}, g.t,
+                                        sd.has_normals ? g_ng : g_ng + g_ns, tp))
+                continue;
+            const bool with_n = grad_normals && sd.has_normals && sd.normal_map < 0 &&
+                                surface_grad_normals(at3(Nv, f[0]), at3(Nv, f[1]), at3(Nv, f[2]), h.u, h.v, g_ns, tn);
+            float *t18 = tm.data() + 18 * (size_t)i;
+            for (int k = 0; k < 3; ++k) {
+                const float pk[3] = {tp[k].x, tp[k].y, tp[k].z};
+                for (int a = 0; a < 3; ++a) {
+                    t18[3 * k + a] = pk[a];
+                    accp[3 * (size_t)f[k] + a] += (double)pk[a];
+                    hasp[3 * (size_t)f[k] + a] = 1;
+                }
+                if (!with_n) continue;
+                const float nk[3] = {tn[k].x, tn[k].y, tn[k].z};
+                for (int a = 0; a < 3; ++a) {
+                    t18[9 + 3 * k + a] = nk[a];
+                    accn[3 * (size_t)f[k] + a] += (double)nk[a];
+                    hasn[3 * (size_t)f[k] + a] = 1;
+                }
+            }
+        }
+        for (size_t k = 0; k < nfl; ++k)
+            if (hasp[k]) grad_positions[k] = (float)((double)grad_positions[k] + accp[k]);
+        for (size_t k = 0; k < hasn.size(); ++k)
+            if (hasn[k]) grad_normals[k] = (float)((double)grad_normals[k] + accn[k]);
+        if (terms) std::memcpy(terms, tm.data(), tm.size() * sizeof(float));
+        return NORI_OK;
+    });
+}
+
+int nori_gpu_surface_grad(nori_gpu_ctx *c, const nori_gpu_surface_grad_desc *gd, const float *rays,
+                          const nori_gpu_hit *hits, const nori_gpu_surface *grad_surf, float *grad_positions,
+                          float *grad_normals, nori_gpu_stats *stats) {
+    return guarded([&] {
+        if (!c || !gd || !rays || !hits || !grad_surf || !grad_positions) return fail(NORI_ERR_INVALID, "null argument");
+        if (gd->reserved[0] != 0 || gd->reserved[1] != 0) return fail(NORI_ERR_INVALID, "nori_gpu_surface_grad: reserved must be 0");
+        if (gd->on_device && ((uintptr_t)rays % 16 || (uintptr_t)hits % 16 || (uintptr_t)grad_surf % 16))
+            return fail(NORI_ERR_INVALID, "nori_gpu_surface_grad: device rays, hits and grad_surf must be 16-byte aligned");
+        if (gd->on_device && ((uintptr_t)grad_positions % 4 || (uintptr_t)grad_normals % 4))
+            return fail(NORI_ERR_INVALID, "nori_gpu_surface_grad: device grad_positions and grad_normals must be 4-byte aligned");
+        if (gd->n == 0) return NORI_OK;
+        return surface_grad(*c, *gd, rays, hits, grad_surf, grad_positions, grad_normals, stats);
     });
 }
 

@@ -27,7 +27,7 @@ from ._abi import NoriError, check, lib  # noqa: F401
 __all__ = ["load_scene", "Scene", "GpuRenderer", "RenderThread", "NoriError", "device_count",
            "develop", "write_exr", "write_png", "read_exr", "film_variance", "ldr_bytes", "variance_gray",
            "denoise", "read_image", "block_error", "film_features", "denoise_guided", "film_denoise_guided",
-           "scene_surface", "bvh_refit", "bvh_rebuild", "film_splat", "film_gather"]
+           "scene_surface", "surface_grad", "bvh_refit", "bvh_rebuild", "film_splat", "film_gather"]
 
 
 def _fptr(a):
@@ -299,6 +299,48 @@ def scene_surface(scene, rays, hits):
     return out
 
 
+def _grad_records(grad_surf, n):
+    """A record gradient as n contiguous 64-byte rows: a SURFACE_DTYPE array or (n, 16) float32."""
+    g = np.asarray(grad_surf)
+    g = np.ascontiguousarray(g) if g.dtype == SURFACE_DTYPE else np.ascontiguousarray(g, dtype=np.float32)
+    if g.nbytes != 64 * n:
+        raise ValueError(f"grad_surf {g.shape} {g.dtype}: expected {n} records of 16 floats")
+    return g
+
+
+def surface_grad(scene, rays, hits, grad_surf, positions=None, normals=None, with_terms=False):
+    """The hit record's adjoint in the mesh vertices, on the host (nori_scene_surface_grad, where it
+    is stated; no GPU needed): for `grad_surf`, the gradient of some scalar in the records of `hits`
+    of `rays` -- a SURFACE_DTYPE array or (n, 16) float32 in the record's layout, of which only p,
+    t, ng and ns are read --, that scalar's gradient in the vertex positions and vertex normals,
+    two (num_vertices, 3) float32 arrays (sums taken in float64).  positions / normals: the
+    geometry to differentiate at, (num_vertices, 3); None: as loaded.  with_terms: also the (n, 18)
+    per-hit terms g_p0, g_p1, g_p2, g_n0, g_n1, g_n2.
+
+    The barycentrics are held for p and ns and the ray for t; the hit set is held.  A caller who
+    wants the point where the fixed ray meets the moving triangle (p = o + t d) adds d . g_p to
+    g_t and passes g_p = 0.  GpuRenderer.surface_grad is the device version."""
+    rays = np.ascontiguousarray(rays, dtype=np.float32)
+    hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE)
+    if rays.ndim != 2 or rays.shape[1] != 8 or hits.shape != (rays.shape[0],):
+        raise ValueError(f"rays {rays.shape} / hits {hits.shape}: expected (n, 8) and (n,)")
+    n, V = rays.shape[0], scene.desc.num_vertices
+    g = _grad_records(grad_surf, n)
+    arrs = []
+    for a, what in ((positions, "positions"), (normals, "normals")):
+        if a is not None:
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            if a.shape != (V, 3):
+                raise ValueError(f"{what} {a.shape}: expected {(V, 3)}")
+        arrs.append(a)
+    gp, gn = np.zeros((V, 3), np.float32), np.zeros((V, 3), np.float32)
+    terms = np.zeros((n, 18), np.float32) if with_terms else None
+    ptr = lambda a: None if a is None else C.c_void_p(a.ctypes.data)  # noqa: E731
+    check(lib().nori_scene_surface_grad(scene.desc_ptr, ptr(arrs[0]), ptr(arrs[1]), n, ptr(rays), ptr(hits), ptr(g),
+                                        ptr(gp), ptr(gn), ptr(terms)))
+    return (gp, gn, terms) if with_terms else (gp, gn)
+
+
 def _guided_args(img, var, feat7, radius, patch, k, eps, sigma_albedo, sigma_normal, sigma_depth):
     img = np.ascontiguousarray(img, dtype=np.float32)
     var = np.ascontiguousarray(var, dtype=np.float32)
@@ -480,6 +522,7 @@ class GpuRenderer:
         self._destroy = lib().nori_gpu_destroy  # usable in __del__ at interpreter exit
         self.device = device
         self.last_stats = None
+        self.geometry_version = 0  # bumped by every successful update_vertices / rebuild_bvh
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -674,6 +717,60 @@ class GpuRenderer:
         self._call(lib().nori_gpu_query, C.byref(qd), C.c_void_p(rays.ctypes.data), C.c_void_p(hits.ctypes.data),
                    None if surf is None else C.c_void_p(surf.ctypes.data))
         return {"hits": hits} if surf is None else {"hits": hits, "surf": surf}
+
+    def surface_grad(self, rays, hits, grad_surf, grad_positions=None, grad_normals=None, n=None):
+        """The hit record's adjoint in the mesh vertices (nori_gpu_surface_grad; stated at
+        nori_scene_surface_grad in nori_gpu.h), for the vertices the context holds now: with
+        `grad_surf` the gradient of some scalar in the records query() gave for `rays` / `hits`
+        (the record's own layout; only p, t, ng and ns are read), that scalar's gradient in the
+        vertex positions and normals is ADDED into grad_positions / grad_normals.
+
+        Host form: rays (n, 8), hits (structured t, prim, u, v), grad_surf (a SURFACE_DTYPE array
+        or (n, 16) float32); returns (grad_positions, grad_normals), two (num_vertices, 3) float32
+        arrays -- the ones given, or new zero ones.
+        Device form: torch tensors or int device addresses (then with n=) for rays, hits and
+        grad_surf (16-byte aligned) and for grad_positions (required) and grad_normals (None: the
+        normal terms are skipped), num_vertices x 3 floats each; everything is used in place and
+        None is returned.  The buffers must be ready before the call.
+
+        The barycentrics are held for p and ns, the ray for t, the hit set throughout; a caller
+        who wants the point where the fixed ray meets the moving triangle (p = o + t d) adds
+        d . g_p to g_t and passes g_p = 0.  Sums of several terms are formed in no fixed order.
+        last_stats: ms_total, ms_shade (the kernel)."""
+        gd = _abi.SurfaceGradDesc()
+        V = self.scene.desc.num_vertices
+        given = (rays, hits, grad_surf)
+        host = [isinstance(a, np.ndarray) for a in given]
+        if any(host) != all(host):
+            raise ValueError("surface_grad: rays, hits and grad_surf must all be numpy arrays or all be device arrays")
+        if not all(host):
+            if grad_positions is None or isinstance(grad_positions, np.ndarray) or isinstance(grad_normals, np.ndarray):
+                raise ValueError("surface_grad: device arrays need a device grad_positions= (and grad_normals=)")
+            if n is None:
+                if not hasattr(rays, "numel"):
+                    raise ValueError("surface_grad: int device addresses need n=")
+                n = rays.numel() // 8
+            gd.n, gd.on_device = int(n), 1
+            self._call(lib().nori_gpu_surface_grad, C.byref(gd), C.c_void_p(_addr(rays)), C.c_void_p(_addr(hits)),
+                       C.c_void_p(_addr(grad_surf)), C.c_void_p(_addr(grad_positions)), C.c_void_p(_addr(grad_normals)))
+            return None
+        rays = np.ascontiguousarray(rays, dtype=np.float32)
+        hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE)
+        if rays.ndim != 2 or rays.shape[1] != 8 or hits.shape != (rays.shape[0],):
+            raise ValueError(f"rays {rays.shape} / hits {hits.shape}: expected (n, 8) and (n,)")
+        if n is not None and int(n) != rays.shape[0]:
+            raise ValueError(f"surface_grad: {rays.shape[0]} rays, expected {int(n)}")
+        g = _grad_records(grad_surf, rays.shape[0])
+        outs = []
+        for a in (grad_positions, grad_normals):
+            if a is None:
+                a = np.zeros((V, 3), np.float32)
+            assert isinstance(a, np.ndarray) and a.dtype == np.float32 and a.flags.c_contiguous and a.size == 3 * V
+            outs.append(a)
+        gd.n = rays.shape[0]
+        self._call(lib().nori_gpu_surface_grad, C.byref(gd), C.c_void_p(rays.ctypes.data), C.c_void_p(hits.ctypes.data),
+                   C.c_void_p(g.ctypes.data), C.c_void_p(outs[0].ctypes.data), C.c_void_p(outs[1].ctypes.data))
+        return outs[0], outs[1]
 
     def camera_rays(self, passes=None, pass_begin=0, blocks=None, seed=0, out=None):
         """Camera::sampleRay of the renderer's own samples (nori_gpu_camera_rays): the primary rays
@@ -989,6 +1086,7 @@ class GpuRenderer:
             torch.cuda.synchronize(self.device)
         st = _abi.UpdateStats()
         check(lib().nori_gpu_update_vertices(self._h, C.byref(ud), C.byref(st)))
+        self.geometry_version += 1
         del keep_p, keep_n
         return st.as_dict()
 
@@ -1004,6 +1102,7 @@ class GpuRenderer:
         rd.leaf_max = leaf_max
         st = _abi.RebuildStats()
         check(lib().nori_gpu_rebuild_bvh(self._h, C.byref(rd), C.byref(st)))
+        self.geometry_version += 1
         return st.as_dict()
 
     def bvh_nodes(self):

@@ -138,6 +138,11 @@ class QueryDesc(C.Structure):
     _fields_ = [("n", C.c_uint32), ("any_hit", C.c_int32), ("on_device", C.c_int32), ("reserved", C.c_uint32)]
 
 
+class SurfaceGradDesc(C.Structure):
+    """nori_gpu_surface_grad_desc: the descriptor of nori_gpu_surface_grad."""
+    _fields_ = [("n", C.c_uint32), ("on_device", C.c_int32), ("reserved", C.c_uint32 * 2)]
+
+
 class ShadingDesc(C.Structure):
     """nori_gpu_shading_desc: the common descriptor of the shading queries."""
     _fields_ = [("n", C.c_uint32), ("on_device", C.c_int32), ("emitter", C.c_int32), ("reserved", C.c_uint32)]
@@ -235,6 +240,10 @@ SIGNATURES = {
     "nori_gpu_query": (C.c_int, [C.c_void_p, C.POINTER(QueryDesc), C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.POINTER(Stats)]),
     "nori_scene_surface": (C.c_int, [C.POINTER(SceneDesc), C.c_uint32, C.POINTER(C.c_float), C.c_void_p, C.c_void_p]),
+    "nori_scene_surface_grad": (C.c_int, [C.POINTER(SceneDesc), C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nori_gpu_surface_grad": (C.c_int, [C.c_void_p, C.POINTER(SurfaceGradDesc), C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.POINTER(Stats)]),
     "nori_gpu_camera_rays": (C.c_int, [C.c_void_p, C.POINTER(RenderDesc), C.c_void_p]),
     "nori_gpu_bsdf_eval": (C.c_int, [C.c_void_p, C.POINTER(ShadingDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nori_gpu_bsdf_sample": (C.c_int, [C.c_void_p, C.POINTER(ShadingDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -285,7 +294,8 @@ ADDED_IN_7 = {"nori_gpu_query", "nori_scene_surface", "nori_gpu_camera_rays", "n
               "nori_scene_shade_rtc", "nori_gpu_shade_rtc_info", "nori_gpu_bsdf_eval", "nori_gpu_bsdf_sample",
               "nori_gpu_emitter_sample", "nori_gpu_emitter_eval", "nori_gpu_sample_uniforms", "nori_film_splat",
               "nori_gpu_film_splat", "nori_gpu_film_splat_passes", "nori_scene_scan_fast", "nori_gpu_li",
-              "nori_film_gather", "nori_gpu_film_gather", "nori_gpu_film_gather_passes"}
+              "nori_film_gather", "nori_gpu_film_gather", "nori_gpu_film_gather_passes", "nori_scene_surface_grad",
+              "nori_gpu_surface_grad"}
 
 COMM_ID_BYTES = 128
 SHARD_PASSES, SHARD_BLOCKS = 0, 1

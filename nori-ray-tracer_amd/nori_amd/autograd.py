@@ -12,11 +12,17 @@ reads the incoming gradient over the window it was splatted into, with the same 
 piecewise constant in the position.  The library runs on its own stream and its calls block, so
 each call is preceded by a synchronisation of torch's current stream on the context's device.
 
+`surface` makes the hit record differentiable in the mesh vertices:
+
+    rec, hits = autograd.surface(r, rays, positions)     # positions.requires_grad: rec carries a graph
+    hit = hits[:, 1].view(torch.int32) >= 0
+    ((rec[hit, 3] - target_t[hit]) ** 2).sum().backward()   # positions.grad, through nori_gpu_surface_grad
+
 This module alone imports torch; `import nori_amd` works without it."""
 import torch
 from torch.autograd.function import once_differentiable
 
-__all__ = ["film_splat", "film_splat_passes", "develop"]
+__all__ = ["film_splat", "film_splat_passes", "develop", "surface"]
 
 
 def _device(r):
@@ -72,6 +78,71 @@ class _FilmSplatPasses(torch.autograd.Function):
         _ready(ctx.r)
         ctx.r.film_gather_passes(pos, grad, val, passes=ctx.passes, blocks=ctx.blocks, out=grad_val)
         return None, None, grad_val, None, None
+
+
+class _Surface(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, r, rays, positions, normals):
+        n = rays.numel() // 8
+        dev = _device(r)
+        _ready(r)
+        r.update_vertices(positions, normals)
+        hits = torch.empty((n, 4), dtype=torch.float32, device=dev)
+        rec = torch.empty((n, 16), dtype=torch.float32, device=dev)
+        _ready(r)
+        if n:
+            r.query(rays.data_ptr(), n=n, hits_out=hits.data_ptr(), surf_out=rec.data_ptr())
+        ctx.r, ctx.version, ctx.with_normals = r, r.geometry_version, normals is not None
+        ctx.save_for_backward(rays, hits)
+        ctx.mark_non_differentiable(hits)
+        return rec, hits
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_rec, _grad_hits):
+        r = ctx.r
+        if r.geometry_version != ctx.version:
+            raise RuntimeError("autograd.surface: the context's geometry has changed since this forward "
+                               "(update_vertices / rebuild_bvh); the backward reads the context's current "
+                               "vertices and would return the gradient at another geometry")
+        rays, hits = ctx.saved_tensors
+        V = r.scene.desc.num_vertices
+        grad_rec = grad_rec.contiguous()
+        gp = torch.zeros((V, 3), dtype=torch.float32, device=grad_rec.device)
+        gn = torch.zeros_like(gp) if ctx.with_normals and ctx.needs_input_grad[3] else None
+        _ready(r)
+        if rays.numel():
+            r.surface_grad(rays, hits, grad_rec, gp, gn, n=rays.numel() // 8)
+        return None, None, gp, gn
+
+
+def surface(r, rays, positions, normals=None):
+    """The hit records of `rays` on the mesh at `positions`, differentiable in the vertices.
+
+    rays (n, 8), positions and normals (num_vertices, 3; normals=None: the vertex normals stay).
+    Forward: r.update_vertices(positions, normals), then r.query(rays) into new tensors.  Returns
+    (rec, hits): the (n, 16) float32 records in nori_gpu_surface's layout -- p 0:3, t 3, ng 4:7,
+    ns 8:11, uv 12:14, bary 14:16; columns 7 and 11 hold the int32 prim and shape as bits -- and the
+    (n, 4) hits (t, prim as bits, u, v; no gradient).  rec carries a graph when positions or
+    normals requires grad; its backward is r.surface_grad (nori_gpu_surface_grad).
+
+    The context's geometry moves to `positions` as a side effect: that is the design, every later
+    call of `r` sees it.  The backward reads the context's vertices, so it raises if
+    update_vertices or rebuild_bvh ran on `r` after this forward.  The context must be able to
+    move its vertices (NORI_TRAVERSAL=bvh for small scenes): update_vertices' NoriError passes
+    through.
+
+    What is differentiated: p and ns at fixed barycentrics, t as the distance at which the fixed
+    ray meets the moving triangle's plane, ng; the hit set is held (no silhouette terms), uv and
+    bary have no gradient, a normal-mapped shape's ns none, spheres none.  For the point where the
+    fixed ray meets the moving surface use rays[:, 0:3] + rec[:, 3:4] * rays[:, 4:7] instead of
+    rec[:, 0:3] (equivalently: fold d . g_p into g_t and pass g_p = 0).  A miss has t = +inf: mask
+    it out of the loss."""
+    rays = _input(r, rays).detach().reshape(-1, 8)
+    positions = _input(r, positions)
+    if normals is not None:
+        normals = _input(r, normals)
+    return _Surface.apply(r, rays, positions, normals)
 
 
 def film_splat(r, pos, val):
