@@ -57,6 +57,11 @@
  *   nori_scene_surface_grad, nori_gpu_surface_grad
  *                         (the hit record's adjoint in the vertex positions and
  *                          normals; no reference counterpart)
+ *   nori_scene_materials, nori_scene_bsdf_grad, nori_gpu_update_materials,
+ *   nori_gpu_materials, nori_gpu_bsdf_grad
+ *                         (differentiable materials: BSDF parameters set on a
+ *                          live context, and bsdf_eval's adjoint in them; no
+ *                          reference counterpart)
  *   nori_scene_scan_rtc, nori_scene_shade_rtc, nori_gpu_shade_rtc_info
  *                         (the scene-specialised kernels compiled at context
  *                          creation through hipRTC; no reference counterpart)
@@ -835,6 +840,155 @@ int nori_gpu_emitter_sample(nori_gpu_ctx *ctx, const nori_gpu_shading_desc *desc
  * path_mis: w_mat = pdf_mat / (pdf_mat + pdf_em) if the sum is > 0. */
 int nori_gpu_emitter_eval(nori_gpu_ctx *ctx, const nori_gpu_shading_desc *desc, const nori_gpu_surface *surf,
                           const float *from, float *out);
+
+/* ---- differentiable materials ---------------------------------------------
+ * The material row: NORI_MATERIAL_FLOATS floats per entry of the scene's
+ * bsdfs[], in its order -- the parameters that may change under a context and
+ * that nori_gpu_bsdf_eval is differentiated in.
+ *   words 0-2    the colour: diffuse albedo (constant_color, or the
+ *                checkerboard's value1) / microfacet kd / disney base_color
+ *   word  3      microfacet alpha
+ *   words 4-9    disney metallic, specular, roughness, sheen, sheen_tint, specular_tint
+ *   words 10-12  checkerboard value2
+ *   words 13-15  reserved: ignored when set, 0 when read, 0 in every gradient
+ * The words in use: diffuse with a constant albedo 0-2, with a checkerboard
+ * 0-2 and 10-12, with an image texture none; microfacet 0-3; disney 0-2 and
+ * 4-9; mirror and dielectric none.  A word that the BSDF's type does not use
+ * is ignored when set (it may hold anything, NaN included), reads 0 and is 0
+ * in every gradient.  Held: the IORs, the checkerboard's delta and scale,
+ * image texels, normal maps, emitters. */
+#define NORI_MATERIAL_FLOATS 16
+
+/* The rows of the scene as loaded: rows[16 b ..] for b < num_bsdfs.  Host only.
+ * NORI_ERR_INVALID: a null argument. */
+int nori_scene_materials(const nori_scene_desc *scene, float *rows);
+
+/* nori_gpu_bsdf_eval's adjoint in the material rows, on the host (no device
+ * needed): for a gradient grad_out[i] of some scalar in output row i of
+ * nori_gpu_bsdf_eval(surf, wi, wo) (its own layout, n x 8 floats), what that
+ * scalar's gradient in the rows receives from element i.  This is the one
+ * statement; nori_gpu_bsdf_grad forms the same terms on the device.
+ *   materials: num_bsdfs x 16 floats, the rows to differentiate at (the derived
+ *     constants ks and disney's pdf alpha follow them as in
+ *     nori_gpu_update_materials); NULL: the scene's own.
+ *   Of grad_out[i] words 0-2 (g_r, g_g, g_b: the gradient in eval) and word 3
+ *     (g_p: in pdf) are read; words 4-7 are never read and may hold anything:
+ *     the cosines do not depend on the parameters.
+ *   Held: surf, wi, wo (no gradient in them), the IORs, textures' layout.
+ * Element i: the frame, to_local, the uv rule and the miss rule are
+ * nori_gpu_bsdf_eval's; b is the BSDF of the record's shape; wi, wo below are
+ * local.  Every operation is fp32, rounded once, in the order written (sums
+ * and products left to right; dot(a, b) = (a.x b.x + a.y b.y) + a.z b.z;
+ * ipi = 1/pi as a float), the forward factors D, F, G1, tan, schlick, ggx,
+ * gtr2 are the routines bsdf_eval itself calls, and a branch of eval (of pdf)
+ * that returns zero gives zero terms for g_r, g_g, g_b (for g_p).
+ *   diffuse, constant:  eval is zero unless wi.z > 0 and wo.z > 0; then
+ *       t[c] = g_c * ipi, c = 0, 1, 2.  pdf has no parameter.
+ *   diffuse, checkerboard: the same three products, at words 0-2 in a cell of
+ *       value1 and at words 10-12 in a cell of value2 (the forward's parity).
+ *   diffuse with an image texture, mirror, dielectric, a miss: a zero row.
+ *   microfacet: h = normalize(wi + wo), D = beckmann_D(h), F = fresnel(h.wi),
+ *       Gi = smith_G1(wi, h), Go = smith_G1(wo, h), den = 4 wi.z wo.z, gs = (g_r + g_g) + g_b
+ *       tt = tan_theta(h) / alpha;  dD = D * (2 * (tt * tt - 1) / alpha)
+ *       dG1(v): 0 where smith_G1 returns early (tan_theta(v) == 0, the sign
+ *         test) or a >= 1.6, a = 1 / (alpha tan_theta(v)); else with
+ *         N = 3.535 a + 2.181 a a, Q = 1 + 2.276 a + 2.577 a a:
+ *         ((3.535 + 4.362 a) * Q - N * (2.276 + 5.154 a)) / (Q * Q) * (-(a / alpha))
+ *       dG = dG1(wi) * Go + Gi * dG1(wo)
+ *       s_ks = D * F * (Gi * Go) / den                      (d eval / d ks)
+ *       s_al = ks * F * (dD * (Gi * Go) + D * dG) / den     (d eval / d alpha)
+ *       pdf is zero unless wo.z > 0; then J = h.z / (4 |h.wo|),
+ *       p_ks = D * J - wo.z * ipi,  p_al = ks * (dD * J);   else p_ks = p_al = 0
+ *       t[c] = g_c * ipi;  t[3] = gs * s_al + g_p * p_al
+ *       ks = 1 - max(kd): t[m] = t[m] - (gs * s_ks + g_p * p_ks) for the first
+ *       channel m that attains the maximum.  F has no term (the IORs are held).
+ *   disney: eval is zero unless wi.z >= 0 and wo.z >= 0; the adjoint of
+ *       disney.cpp's expression written out in csrc/bsdf_grad.h, with these
+ *       conventions: alpha = max(0.001, r r) has derivative 2 r where
+ *       r r > 0.001 and 0 elsewhere (the eval's float square and the pdf's
+ *       double square each by its own comparison); ctint = base / l carries
+ *       the derivative through l = luminance(base) where l > 0, else none;
+ *       fd90's roughness term counts; gtr2's zero branch has derivative 0.
+ *       pdf is zero unless wo.z > 0.
+ *   A row in which any float comes out non-finite, or whose g_r, g_g, g_b or
+ *   g_p is non-finite, is replaced by zeros as a whole (den = 0 at grazing
+ *   directions, an overflowing lobe): one bad sample does not poison a sum.
+ * terms (NULL, or n x 16 floats): the row of element i at terms[16 i].
+ * The sums: grad_materials[16 b + w] receives word w of every element on BSDF
+ * b, accumulated in float64 in element order and added once, in float64, to
+ * the value already there and rounded to fp32; a destination that receives no
+ * non-zero term is not touched.
+ * NORI_ERR_INVALID, nothing written: a null scene, surf, wi, wo, grad_out or
+ * grad_materials; a record whose shape is < -1 or >= num_shapes. */
+int nori_scene_bsdf_grad(const nori_scene_desc *scene, const float *materials, uint32_t n,
+                         const nori_gpu_surface *surf, const float *wi, const float *wo, const float *grad_out,
+                         float *grad_materials, float *terms);
+
+/* Set every BSDF's parameter words from `rows` (num_bsdfs x 16 floats, host
+ * memory, or device memory used in place when on_device: 4-byte aligned) and
+ * recompute the derived constants (microfacet ks = 1 - max(kd), disney's pdf
+ * alpha = max(1e-3, r r) squared in double) with nori_gpu_create's own
+ * operations.  Both copies of the BSDF table are updated (the small-scene
+ * blob's too), so every later render, li, feature pass and shading query sees
+ * the new values, bit-identical to a context created from a scene loaded with
+ * them.  No plan decision and no scene-specialised kernel depends on a
+ * parameter value (only on BSDF types and texture kinds, which are held), so
+ * this works in either traversal mode.  Blocking, on the context's stream.
+ * Refused with nothing changed -- NORI_ERR_INVALID: a null argument, num_bsdfs
+ * other than the scene's, reserved != 0, on_device with a misaligned pointer
+ * or one that is not device memory, a non-finite float in a word in use
+ * (counted on the device in a pass of its own before anything is modified);
+ * NORI_ERR_UNSUPPORTED: a photonmapper context (its map was traced at
+ * creation).  Every success bumps the context's materials version. */
+typedef struct nori_gpu_materials_desc {
+    uint32_t num_bsdfs;    /* must equal the scene's */
+    int32_t  on_device;    /* rows is a device pointer on the context's device */
+    uint32_t reserved[2];  /* must be 0 */
+} nori_gpu_materials_desc;
+int nori_gpu_update_materials(nori_gpu_ctx *ctx, const nori_gpu_materials_desc *desc, const float *rows);
+/* The rows the context holds now (host array, num_bsdfs x 16; may be NULL) and
+ * the number of successful nori_gpu_update_materials calls so far (may be NULL). */
+int nori_gpu_materials(nori_gpu_ctx *ctx, float *rows, uint64_t *version);
+
+/* nori_scene_bsdf_grad on the device, for the materials the context holds now.
+ * The kernel forms the statement's terms (bit for bit where the forward has
+ * no transcendental: diffuse, checkerboard, disney; microfacet to the device
+ * library's expf) and ADDS their sums into grad_materials (num_bsdfs x 16).
+ * Reproducible: up to NORI_BSDF_GRAD_MAX_TABLE BSDFs the sums are formed
+ * without atomics -- per wave in a fixed order, per work-group in wave order
+ * into one slab of partial sums, the slabs in slab order by a second kernel,
+ * which adds each destination once -- so the same inputs give the same bits on
+ * every call, whatever the device's scheduling.  (A destination's value is
+ * the fp32 sum of its terms in that fixed tree, within m 2^-24 A of the
+ * statement's for m terms of magnitude sum A.)  With more BSDFs, or with
+ * NORI_BSDF_GRAD_TABLE=0 in the environment, the sums of a wave's elements on
+ * one BSDF are added with float atomics: their order is not fixed, and neither
+ * are the last bits.
+ * on_device: surf, grad_out, grad_materials, terms (16-byte aligned) and wi,
+ * wo (4-byte aligned) are device memory used in place.  Otherwise host arrays,
+ * staged through context buffers in chunks of whole tiles of 256 elements, at
+ * most NORI_QUERY_CHUNK elements (at least one tile); the chunks continue one
+ * set of partial sums, so the chunking does not show in the bits; the sums are
+ * formed in a zeroed device buffer and added to the caller's array once at
+ * the end.  Nothing is allocated per call once the
+ * context's buffers have grown to the call's size.  terms may be NULL.  Works
+ * on a context of any integrator and either traversal mode.  Blocking, on the
+ * context's stream.  n == 0 is a no-op.
+ * NORI_ERR_INVALID, nothing launched and nothing written: a null ctx, desc,
+ * surf, wi, wo, grad_out or grad_materials; reserved != 0; on_device with a
+ * misaligned pointer or one that is not device memory; host records with a
+ * shape < -1 or >= num_shapes (device records: such an element adds nothing).
+ * stats (may be NULL): ms_total (wall time), ms_shade = HIP-event time of the kernels. */
+#define NORI_BSDF_GRAD_MAX_TABLE 64
+typedef struct nori_gpu_bsdf_grad_desc {
+    uint32_t n;            /* elements */
+    int32_t  on_device;    /* every array is a device pointer on the context's device */
+    uint32_t reserved[2];  /* must be 0 */
+} nori_gpu_bsdf_grad_desc;
+int nori_gpu_bsdf_grad(nori_gpu_ctx *ctx, const nori_gpu_bsdf_grad_desc *desc, const nori_gpu_surface *surf,
+                       const float *wi, const float *wo, const float *grad_out, float *grad_materials,
+                       float *terms, nori_gpu_stats *stats);
+
 /* The renderer's own random numbers, the companion of nori_gpu_camera_rays:
  * draws [first, first + count) of Sampler::next1D on the stream of sample
  * (pass pass_begin + k, pixel pix = y W + x), wave_seed(seed, (pass_begin + k)

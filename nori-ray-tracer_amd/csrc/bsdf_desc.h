@@ -9,6 +9,7 @@
 
 #include "../../include/nori_gpu.h"
 #include "dev_records.h"
+#include "material_row.h"
 
 namespace nori {
 
@@ -24,17 +25,13 @@ inline void dev_bsdf_from_desc(const nori_bsdf_desc &b, DevBsdf &o) {
     o.eta_ie = b.int_ior / b.ext_ior;
     o.inv_eta_ei = 1 / o.eta_ei;
     o.alpha = b.alpha;
-    float mk = b.kd[0] < b.kd[1] ? b.kd[1] : b.kd[0];
-    mk = mk < b.kd[2] ? b.kd[2] : mk;
-    o.ks = 1 - mk;  // microfacet.cpp:45
     o.metallic = b.metallic;
     o.specular = b.specular;
     o.roughness = b.roughness;
     o.sheen = b.sheen;
     o.sheen_tint = b.sheen_tint;
     o.spec_tint = b.specular_tint;
-    double r2 = (double)b.roughness * (double)b.roughness;  // disney.cpp:59
-    o.d_alpha = (float)(r2 > 1e-3 ? r2 : 1e-3);
+    bsdf_derived(o);  // ks and d_alpha (material_row.h: nori_gpu_update_materials recomputes them with it)
     o.tex = b.albedo_texture;
     for (int k = 0; k < 3; ++k) o.tex_v2[k] = b.tex_value2[k];
     for (int k = 0; k < 2; ++k) o.tex_delta[k] = b.tex_delta[k], o.tex_scale[k] = b.tex_scale[k];

@@ -1,7 +1,7 @@
 // ctx.h -- the runtime units' private view of a context: nori_gpu_ctx and
 // nori_gpu_comm, device buffers, HIP error handling, the kernel clock, the
 // film target, and the few functions that cross units.  Included by upload.hip, render.hip, queries.hip,
-// film_splat.hip, li.hip, adaptive.hip, dynamic.hip and sharded.hip only.
+// film_splat.hip, li.hip, adaptive.hip, dynamic.hip, materials.hip and sharded.hip only.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -177,6 +177,12 @@ struct nori_gpu_ctx {
     DevBuf rb_box, rb_keys[2], rb_sort_tmp, rb_scan_tmp, rb_prims, rb_nodes, rb_refs, rb_ranges[2], rb_ends, rb_count,
         rb_scan, rb_inner, rb_leaf, rb_slots;
     hipEvent_t rb_ev[2] = {};
+    // nori_gpu_update_materials / nori_gpu_bsdf_grad (materials.hip): the scene's BSDF count, the
+    // successful updates so far, staging of host rows (also the host form's zeroed sums), the
+    // table path's slabs of partial sums, staging of host gradient rows and of the terms
+    uint32_t num_bsdfs = 0;
+    uint64_t materials_version = 0;
+    DevBuf mat_rows, bg_slabs, bg_gout, bg_terms;
     std::vector<DevShape> hshapes;
     std::vector<EmitterMesh> emitter_meshes;
     uint32_t pool_cap = 0;

@@ -368,12 +368,21 @@ ND V3 albedo_at(const DevBsdf &b, V2 uv) {
     const int y = (int)fabsf(floorf(uv.y / b.tex_scale[1] - b.tex_delta[1]));
     return x % 2 == y % 2 ? V3{b.albedo[0], b.albedo[1], b.albedo[2]} : V3{b.tex_v2[0], b.tex_v2[1], b.tex_v2[2]};
 }
+// The checkerboard cell albedo_at shows at uv, true where value1 (the albedo):
+// its two conversions and its test, for the adjoint's routing (bsdf_grad.h),
+// which the host compiles too.  (albedo_at keeps its own copy: its code is the
+// render kernels' and stays as it was.)
+NHD bool checker_value1(const DevBsdf &b, V2 uv) {
+    const int x = (int)fabsf(floorf(uv.x / b.tex_scale[0] - b.tex_delta[0]));
+    const int y = (int)fabsf(floorf(uv.y / b.tex_scale[1] - b.tex_delta[1]));
+    return x % 2 == y % 2;
+}
 
-ND float beckmann_D(const DevBsdf &b, V3 m) {  // microfacet.cpp:47-53
+NHD float beckmann_D(const DevBsdf &b, V3 m) {  // microfacet.cpp:47-53
     float temp = tan_theta(m) / b.alpha, ct = m.z, ct2 = ct * ct;
     return expf(-temp * temp) / (kPi * b.alpha * b.alpha * ct2 * ct2);
 }
-ND float smith_G1(const DevBsdf &b, V3 v, V3 m) {  // microfacet.cpp:56-76
+NHD float smith_G1(const DevBsdf &b, V3 v, V3 m) {  // microfacet.cpp:56-76
     float tanTheta = tan_theta(v);
     if (tanTheta == 0.0f) return 1.0f;
     if (dot(m, v) * v.z <= 0) return 0.0f;
@@ -382,16 +391,16 @@ ND float smith_G1(const DevBsdf &b, V3 v, V3 m) {  // microfacet.cpp:56-76
     float a2 = a * a;
     return (3.535f * a + 2.181f * a2) / (1.0f + 2.276f * a + 2.577f * a2);
 }
-ND float schlick(float u) {  // disney.cpp:25-29: pow(m, 5) in double
+NHD float schlick(float u) {  // disney.cpp:25-29: pow(m, 5) in double
     double m = (double)clampf_(1 - u, 0.0f, 1.0f);
     double m2 = m * m;
     return (float)(m2 * m2 * m);
 }
-ND float ggx(float NdotV, float alphaG) {  // disney.cpp:31-36
+NHD float ggx(float NdotV, float alphaG) {  // disney.cpp:31-36
     float a = alphaG * alphaG, b = NdotV * NdotV;
     return rcp_full(NdotV + sqrtf(a + b - a * b));
 }
-ND V3 lerp3(float t, V3 a, V3 c) { return a * (1.0f - t) + c * t; }  // disney.cpp:40-42
+NHD V3 lerp3(float t, V3 a, V3 c) { return a * (1.0f - t) + c * t; }  // disney.cpp:40-42
 
 template <bool FULL = true>
 ND V3 bsdf_eval(const DevBsdf &b, const BRec &r) {

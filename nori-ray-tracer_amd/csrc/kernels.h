@@ -3,6 +3,7 @@
 // launch_tail_prefix and launch_finish in kernels_finish.hip; launch_features
 // in kernels_features.hip; launch_surface and launch_camera_rays in
 // kernels_query.hip; the shading queries in kernels_shading.hip; the
+// materials' adjoint and update in kernels_bsdf_grad.hip; the
 // denoisers, the block error and the refit in denoise.hip, block_error.hip
 // and refit.hip; the caller-fed film splats in kernels_film.hip; launch_li in
 // kernels_li.hip; all others in kernels.hip.
@@ -171,6 +172,34 @@ hipError_t launch_surface(const DevScene &S, const float4 *rays, const float4 *h
 hipError_t launch_surface_grad(const DevScene &S, uint32_t num_vertices, const float4 *rays, const float4 *hits,
                                const float4 *grad_surf, uint32_t n, float *grad_positions, float *grad_normals,
                                hipStream_t st);
+// bsdf_eval's adjoint in the material rows (kernels_bsdf_grad.hip; stated at
+// nori_scene_bsdf_grad in nori_gpu.h).  launch_bsdf_grad: the rows of
+// elements [first, first + n) of an array of N elements (the pointers are at
+// element `first`, a multiple of bsdf_grad_tile(); slabs_n = bsdf_grad_slabs(N));
+// terms (may be null) receives each element's row.  surf (four float4 per
+// element), grad_out (two), terms (four) and slabs are 16-byte aligned; all
+// device memory.  bsdf_grad_table(num_bsdfs): the reproducible path without
+// atomics runs (up to NORI_BSDF_GRAD_MAX_TABLE BSDFs, unless
+// NORI_BSDF_GRAD_TABLE=0): the sums go to `slabs` (slabs_n x num_bsdfs x 16
+// floats; the launch for first = 0 starts them, later ones continue them) and
+// launch_bsdf_grad_sum, after the last chunk, ADDS the slabs' sums into
+// grad_materials (num_bsdfs x 16 floats).  Otherwise launch_bsdf_grad adds
+// into grad_materials with float atomics and launch_bsdf_grad_sum does nothing.
+uint32_t bsdf_grad_slabs(uint32_t n);
+uint32_t bsdf_grad_tile();
+bool bsdf_grad_table(uint32_t num_bsdfs);
+hipError_t launch_bsdf_grad(const DevScene &S, uint32_t num_shapes, uint32_t num_bsdfs, const float4 *surf,
+                            const float *wi, const float *wo, const float4 *grad_out, uint32_t n, uint32_t first,
+                            uint32_t slabs_n, float *grad_materials, float4 *terms, float *slabs, hipStream_t st);
+hipError_t launch_bsdf_grad_sum(uint32_t num_bsdfs, const float *slabs, uint32_t slabs_n, float *grad_materials,
+                                hipStream_t st);
+// nori_gpu_update_materials: *count += the non-finite floats among the words in
+// use of rows (num_bsdfs x 16 floats); then each row set into its record of
+// bsdfs and, unless null, of the blob's copy.
+hipError_t launch_materials_count(const DevBsdf *bsdfs, const float *rows, uint32_t num_bsdfs, uint32_t *count,
+                                  hipStream_t st);
+hipError_t launch_materials_set(DevBsdf *bsdfs, DevBsdf *blob_bsdfs, const float *rows, uint32_t num_bsdfs,
+                                hipStream_t st);
 // Primary rays (kernels_query.hip k_camera_rays): the ray of sample (pass
 // pass_begin + k, pixel pix) for k in [k0, k0 + np) and the M entries of
 // `pixels` (y*W + x), written at rays[8 * (k * W * H + pix)]; np * M < 2^31.

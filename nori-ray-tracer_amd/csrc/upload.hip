@@ -175,6 +175,7 @@ void upload_scene(nori_gpu_ctx &c, const nori_scene_desc &d, ScenePlan &p) {
     c.finish_first = p.finish_first;
     c.scene_bytes = c.nodes.bytes + c.prims.bytes;
     c.num_vertices = d.num_vertices;
+    c.num_bsdfs = d.num_bsdfs;
     c.cam = d.camera;
     fill_tables(c, p, offs);
     fill_camera(c.S, d.camera, p);

@@ -27,7 +27,7 @@ from ._abi import NoriError, check, lib  # noqa: F401
 __all__ = ["load_scene", "Scene", "GpuRenderer", "RenderThread", "NoriError", "device_count",
            "develop", "write_exr", "write_png", "read_exr", "film_variance", "ldr_bytes", "variance_gray",
            "denoise", "read_image", "block_error", "film_features", "denoise_guided", "film_denoise_guided",
-           "scene_surface", "surface_grad", "bvh_refit", "bvh_rebuild", "film_splat", "film_gather"]
+           "scene_surface", "surface_grad", "scene_materials", "bsdf_grad", "bvh_refit", "bvh_rebuild", "film_splat", "film_gather"]
 
 
 def _fptr(a):
@@ -339,6 +339,56 @@ def surface_grad(scene, rays, hits, grad_surf, positions=None, normals=None, wit
     check(lib().nori_scene_surface_grad(scene.desc_ptr, ptr(arrs[0]), ptr(arrs[1]), n, ptr(rays), ptr(hits), ptr(g),
                                         ptr(gp), ptr(gn), ptr(terms)))
     return (gp, gn, terms) if with_terms else (gp, gn)
+
+
+MATERIAL_FLOATS = _abi.MATERIAL_FLOATS
+
+
+def scene_materials(scene):
+    """The scene's material rows as loaded (nori_scene_materials): (num_bsdfs, 16) float32, one row
+    per entry of the scene's bsdfs -- words 0-2 the colour (diffuse albedo / checkerboard value1,
+    microfacet kd, disney base_color), 3 microfacet alpha, 4-9 disney metallic, specular,
+    roughness, sheen, sheen_tint, specular_tint, 10-12 checkerboard value2, 13-15 reserved; words a
+    BSDF's type does not use are 0."""
+    rows = np.zeros((scene.desc.num_bsdfs, MATERIAL_FLOATS), np.float32)
+    check(lib().nori_scene_materials(scene.desc_ptr, C.c_void_p(rows.ctypes.data)))
+    return rows
+
+
+def _shading_inputs(name, surf, wi, wo, grad_out):
+    """The host arrays of a bsdf_grad call, checked: records, (n, 3) directions, (n, 8) gradient rows."""
+    surf = np.ascontiguousarray(surf, dtype=SURFACE_DTYPE).reshape(-1)
+    n = surf.shape[0]
+    wi, wo = np.ascontiguousarray(wi, dtype=np.float32), np.ascontiguousarray(wo, dtype=np.float32)
+    g = np.ascontiguousarray(grad_out, dtype=np.float32)
+    if wi.shape != (n, 3) or wo.shape != (n, 3) or g.shape != (n, 8):
+        raise ValueError(f"{name}: wi {wi.shape}, wo {wo.shape}, grad_out {g.shape}: expected {(n, 3)}, {(n, 3)}, {(n, 8)}")
+    return surf, wi, wo, g, n
+
+
+def bsdf_grad(scene, surf, wi, wo, grad_out, materials=None, grad_materials=None, with_terms=False):
+    """bsdf_eval's adjoint in the material rows, on the host (nori_scene_bsdf_grad, where it is
+    stated; no GPU needed): for `grad_out`, the (n, 8) gradient of some scalar in the rows
+    GpuRenderer.bsdf_eval(surf, wi, wo) returns -- columns 0-2 (eval) and 3 (pdf) are read, 4-7
+    never --, that scalar's gradient in the material rows, ADDED into grad_materials ((num_bsdfs,
+    16) float32; None: a new zero array), sums taken in float64.  materials: the rows to
+    differentiate at; None: the scene's own (scene_materials).  with_terms: also the (n, 16)
+    per-element rows.  No gradient in surf, wi or wo."""
+    surf, wi, wo, g, n = _shading_inputs("bsdf_grad", surf, wi, wo, grad_out)
+    nb = scene.desc.num_bsdfs
+    if materials is not None:
+        materials = np.ascontiguousarray(materials, dtype=np.float32)
+        if materials.shape != (nb, MATERIAL_FLOATS):
+            raise ValueError(f"materials {materials.shape}: expected {(nb, MATERIAL_FLOATS)}")
+    if grad_materials is None:
+        grad_materials = np.zeros((nb, MATERIAL_FLOATS), np.float32)
+    assert (isinstance(grad_materials, np.ndarray) and grad_materials.dtype == np.float32 and
+            grad_materials.flags.c_contiguous and grad_materials.shape == (nb, MATERIAL_FLOATS))
+    terms = np.zeros((n, MATERIAL_FLOATS), np.float32) if with_terms else None
+    ptr = lambda a: None if a is None else C.c_void_p(a.ctypes.data)  # noqa: E731
+    check(lib().nori_scene_bsdf_grad(scene.desc_ptr, ptr(materials), n, ptr(surf), ptr(wi), ptr(wo), ptr(g),
+                                     ptr(grad_materials), ptr(terms)))
+    return (grad_materials, terms) if with_terms else grad_materials
 
 
 def _guided_args(img, var, feat7, radius, patch, k, eps, sigma_albedo, sigma_normal, sigma_depth):
@@ -771,6 +821,101 @@ class GpuRenderer:
         self._call(lib().nori_gpu_surface_grad, C.byref(gd), C.c_void_p(rays.ctypes.data), C.c_void_p(hits.ctypes.data),
                    C.c_void_p(g.ctypes.data), C.c_void_p(outs[0].ctypes.data), C.c_void_p(outs[1].ctypes.data))
         return outs[0], outs[1]
+
+    @property
+    def materials_version(self):
+        """The number of successful update_materials calls on this context so far."""
+        v = C.c_uint64()
+        check(lib().nori_gpu_materials(self._h, None, C.byref(v)))
+        return int(v.value)
+
+    def materials(self):
+        """The material rows the context holds now (nori_gpu_materials): (num_bsdfs, 16) float32 in
+        scene_materials' layout."""
+        rows = np.zeros((self.scene.desc.num_bsdfs, MATERIAL_FLOATS), np.float32)
+        check(lib().nori_gpu_materials(self._h, C.c_void_p(rows.ctypes.data), None))
+        return rows
+
+    def update_materials(self, rows):
+        """Set every BSDF's parameters from material rows (nori_gpu_update_materials): every later
+        render, li, feature pass and shading query of this context sees them, bit-identical to a
+        context created from a scene loaded with these values.
+
+        rows: (num_bsdfs, 16) float32 in scene_materials' layout -- a numpy array, a torch tensor
+        on the context's device (used in place; work queued on it is waited for first) or an int
+        device address.  Words a BSDF's type does not use are ignored.  A non-finite value in a
+        word in use, a wrong shape and a photonmapper context raise (NoriError / ValueError) with
+        nothing changed.  `self.scene` keeps describing the materials as loaded."""
+        md = _abi.MaterialsDesc()
+        nb = self.scene.desc.num_bsdfs
+        md.num_bsdfs = nb
+        keep = rows
+        if isinstance(rows, np.ndarray):
+            keep = np.ascontiguousarray(rows, dtype=np.float32)
+            if keep.shape != (nb, MATERIAL_FLOATS):
+                raise ValueError(f"rows {keep.shape}: expected {(nb, MATERIAL_FLOATS)}")
+            p = keep.ctypes.data
+        elif hasattr(rows, "data_ptr"):
+            if tuple(rows.shape) != (nb, MATERIAL_FLOATS) or "float32" not in str(rows.dtype) or not rows.is_contiguous():
+                raise ValueError(f"rows: expected a contiguous float32 tensor of shape {(nb, MATERIAL_FLOATS)}")
+            if not rows.is_cuda or (rows.device.index or 0) != self.device:
+                raise ValueError(f"rows: a tensor on {rows.device}, the context is on device {self.device}")
+            import torch  # (the caller's: a tensor was passed)
+
+            torch.cuda.synchronize(self.device)
+            p, md.on_device = rows.data_ptr(), 1
+        else:
+            p, md.on_device = int(rows), 1
+        check(lib().nori_gpu_update_materials(self._h, C.byref(md), C.c_void_p(p)))
+        del keep
+
+    def bsdf_grad(self, surf, wi, wo, grad_out, grad_materials=None, terms=None, n=None):
+        """bsdf_eval's adjoint in the material rows (nori_gpu_bsdf_grad; stated at
+        nori_scene_bsdf_grad in nori_gpu.h), for the materials the context holds now: with
+        `grad_out` the (n, 8) gradient of some scalar in the rows bsdf_eval(surf, wi, wo) returns
+        (columns 0-2 and 3 are read, 4-7 never), that scalar's gradient in the material rows is
+        ADDED into grad_materials.
+
+        Host form: numpy arrays; returns grad_materials ((num_bsdfs, 16) float32: the one given, or
+        a new zero one), or (grad_materials, terms) with terms=True (the (n, 16) per-element rows).
+        Device form: torch tensors or int device addresses (then with n=) for surf, wi, wo and
+        grad_out, and for grad_materials (required) and terms (optional; n x 16 floats); everything
+        is used in place and None is returned.  The buffers must be ready before the call.
+
+        Up to 64 BSDFs the sums are formed without atomics in a fixed order: the same inputs give
+        the same bits on every call, host or device form, whatever NORI_QUERY_CHUNK.  No gradient
+        in surf, wi or wo.  last_stats: ms_total, ms_shade (the kernels)."""
+        gd = _abi.BsdfGradDesc()
+        nb = self.scene.desc.num_bsdfs
+        given = (surf, wi, wo, grad_out)
+        host = [isinstance(a, np.ndarray) for a in given]
+        if any(host) != all(host):
+            raise ValueError("bsdf_grad: surf, wi, wo and grad_out must all be numpy arrays or all be device arrays")
+        if not all(host):
+            if grad_materials is None or isinstance(grad_materials, np.ndarray) or isinstance(terms, (np.ndarray, bool)):
+                raise ValueError("bsdf_grad: device arrays need a device grad_materials= (and terms=)")
+            if n is None:
+                if not hasattr(wi, "numel"):
+                    raise ValueError("bsdf_grad: int device addresses need n=")
+                n = wi.numel() // 3
+            gd.n, gd.on_device = int(n), 1
+            self._call(lib().nori_gpu_bsdf_grad, C.byref(gd), C.c_void_p(_addr(surf)), C.c_void_p(_addr(wi)),
+                       C.c_void_p(_addr(wo)), C.c_void_p(_addr(grad_out)), C.c_void_p(_addr(grad_materials)),
+                       C.c_void_p(_addr(terms)))
+            return None
+        surf, wi, wo, g, cnt = _shading_inputs("bsdf_grad", surf, wi, wo, grad_out)
+        if n is not None and int(n) != cnt:
+            raise ValueError(f"bsdf_grad: {cnt} elements, expected {int(n)}")
+        if grad_materials is None:
+            grad_materials = np.zeros((nb, MATERIAL_FLOATS), np.float32)
+        assert (isinstance(grad_materials, np.ndarray) and grad_materials.dtype == np.float32 and
+                grad_materials.flags.c_contiguous and grad_materials.shape == (nb, MATERIAL_FLOATS))
+        tm = np.zeros((cnt, MATERIAL_FLOATS), np.float32) if terms else None
+        gd.n = cnt
+        self._call(lib().nori_gpu_bsdf_grad, C.byref(gd), C.c_void_p(surf.ctypes.data), C.c_void_p(wi.ctypes.data),
+                   C.c_void_p(wo.ctypes.data), C.c_void_p(g.ctypes.data), C.c_void_p(grad_materials.ctypes.data),
+                   None if tm is None else C.c_void_p(tm.ctypes.data))
+        return (grad_materials, tm) if terms else grad_materials
 
     def camera_rays(self, passes=None, pass_begin=0, blocks=None, seed=0, out=None):
         """Camera::sampleRay of the renderer's own samples (nori_gpu_camera_rays): the primary rays

@@ -143,6 +143,20 @@ class SurfaceGradDesc(C.Structure):
     _fields_ = [("n", C.c_uint32), ("on_device", C.c_int32), ("reserved", C.c_uint32 * 2)]
 
 
+class MaterialsDesc(C.Structure):
+    """nori_gpu_materials_desc: the descriptor of nori_gpu_update_materials."""
+    _fields_ = [("num_bsdfs", C.c_uint32), ("on_device", C.c_int32), ("reserved", C.c_uint32 * 2)]
+
+
+class BsdfGradDesc(C.Structure):
+    """nori_gpu_bsdf_grad_desc: the descriptor of nori_gpu_bsdf_grad."""
+    _fields_ = [("n", C.c_uint32), ("on_device", C.c_int32), ("reserved", C.c_uint32 * 2)]
+
+
+MATERIAL_FLOATS = 16
+BSDF_GRAD_MAX_TABLE = 64
+
+
 class ShadingDesc(C.Structure):
     """nori_gpu_shading_desc: the common descriptor of the shading queries."""
     _fields_ = [("n", C.c_uint32), ("on_device", C.c_int32), ("emitter", C.c_int32), ("reserved", C.c_uint32)]
@@ -244,6 +258,13 @@ SIGNATURES = {
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nori_gpu_surface_grad": (C.c_int, [C.c_void_p, C.POINTER(SurfaceGradDesc), C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.POINTER(Stats)]),
+    "nori_scene_materials": (C.c_int, [C.POINTER(SceneDesc), C.c_void_p]),
+    "nori_scene_bsdf_grad": (C.c_int, [C.POINTER(SceneDesc), C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nori_gpu_update_materials": (C.c_int, [C.c_void_p, C.POINTER(MaterialsDesc), C.c_void_p]),
+    "nori_gpu_materials": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
+    "nori_gpu_bsdf_grad": (C.c_int, [C.c_void_p, C.POINTER(BsdfGradDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.POINTER(Stats)]),
     "nori_gpu_camera_rays": (C.c_int, [C.c_void_p, C.POINTER(RenderDesc), C.c_void_p]),
     "nori_gpu_bsdf_eval": (C.c_int, [C.c_void_p, C.POINTER(ShadingDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nori_gpu_bsdf_sample": (C.c_int, [C.c_void_p, C.POINTER(ShadingDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -295,7 +316,8 @@ ADDED_IN_7 = {"nori_gpu_query", "nori_scene_surface", "nori_gpu_camera_rays", "n
               "nori_gpu_emitter_sample", "nori_gpu_emitter_eval", "nori_gpu_sample_uniforms", "nori_film_splat",
               "nori_gpu_film_splat", "nori_gpu_film_splat_passes", "nori_scene_scan_fast", "nori_gpu_li",
               "nori_film_gather", "nori_gpu_film_gather", "nori_gpu_film_gather_passes", "nori_scene_surface_grad",
-              "nori_gpu_surface_grad"}
+              "nori_gpu_surface_grad", "nori_scene_materials", "nori_scene_bsdf_grad", "nori_gpu_update_materials",
+              "nori_gpu_materials", "nori_gpu_bsdf_grad"}
 
 COMM_ID_BYTES = 128
 SHARD_PASSES, SHARD_BLOCKS = 0, 1

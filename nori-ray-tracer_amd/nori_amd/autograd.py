@@ -18,11 +18,16 @@ each call is preceded by a synchronisation of torch's current stream on the cont
     hit = hits[:, 1].view(torch.int32) >= 0
     ((rec[hit, 3] - target_t[hit]) ** 2).sum().backward()   # positions.grad, through nori_gpu_surface_grad
 
+`bsdf_eval` makes the shading query differentiable in the material rows:
+
+    out = autograd.bsdf_eval(r, surf, wi, wo, materials)  # materials.requires_grad: out carries a graph
+    (out[:, 0:3] * weight).sum().backward()                 # materials.grad, through nori_gpu_bsdf_grad
+
 This module alone imports torch; `import nori_amd` works without it."""
 import torch
 from torch.autograd.function import once_differentiable
 
-__all__ = ["film_splat", "film_splat_passes", "develop", "surface"]
+__all__ = ["film_splat", "film_splat_passes", "develop", "surface", "bsdf_eval"]
 
 
 def _device(r):
@@ -143,6 +148,56 @@ def surface(r, rays, positions, normals=None):
     if normals is not None:
         normals = _input(r, normals)
     return _Surface.apply(r, rays, positions, normals)
+
+
+class _BsdfEval(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, r, surf, wi, wo, materials):
+        n = wi.numel() // 3
+        _ready(r)
+        r.update_materials(materials)
+        out = torch.empty((n, 8), dtype=torch.float32, device=_device(r))
+        if n:
+            r.bsdf_eval(surf, wi, wo, n=n, out=out)
+        ctx.r, ctx.version = r, r.materials_version
+        ctx.save_for_backward(surf, wi, wo)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        r = ctx.r
+        if r.materials_version != ctx.version:
+            raise RuntimeError("autograd.bsdf_eval: the context's materials have changed since this forward "
+                               "(update_materials); the backward reads the context's current materials and "
+                               "would return the gradient at other values")
+        surf, wi, wo = ctx.saved_tensors
+        grad_out = grad_out.contiguous()
+        gm = torch.zeros((r.scene.desc.num_bsdfs, 16), dtype=torch.float32, device=grad_out.device)
+        _ready(r)
+        if wi.numel():
+            r.bsdf_grad(surf, wi, wo, grad_out, grad_materials=gm, n=wi.numel() // 3)
+        return None, None, None, None, gm
+
+
+def bsdf_eval(r, surf, wi, wo, materials):
+    """GpuRenderer.bsdf_eval at the material rows `materials`, differentiable in them.
+
+    surf (n, 16) float32 records (query()'s, as a tensor), wi and wo (n, 3), materials (num_bsdfs,
+    16) in scene_materials' layout.  Forward: r.update_materials(materials), then r.bsdf_eval into
+    a new (n, 8) tensor (eval rgb, pdf, wo_local.z, wi_local.z, 0, 0).  Backward: r.bsdf_grad
+    (nori_gpu_bsdf_grad) into a zero (num_bsdfs, 16) tensor; words a BSDF's type does not use,
+    and the reserved ones, receive 0.
+
+    The context's materials move to `materials` as a side effect: that is the design, every later
+    render and query of `r` sees them.  The backward reads the context's materials, so it raises
+    if update_materials ran on `r` after this forward.  There is no gradient in surf, wi or wo (they
+    are detached), none in the IORs, textures' layout or image texels; the cosines in columns 4-5
+    do not depend on the materials."""
+    surf = _input(r, surf).detach().reshape(-1, 16)
+    wi = _input(r, wi).detach().reshape(-1, 3)
+    wo = _input(r, wo).detach().reshape(-1, 3)
+    return _BsdfEval.apply(r, surf, wi, wo, _input(r, materials))
 
 
 def film_splat(r, pos, val):
